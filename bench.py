@@ -10,11 +10,15 @@ synthetic R2R-shaped batch per GPU: BASELINE.json configs[1] -- scripts/pt_r2r.b
 autocast-style bf16 (fp32 masters), task mix mlm.5.sap.5.masksem.1, dropout 0.1 -- with inputs resident in HBM.
 Weak scaling: the per-GPU batch is fixed, ranks draw different batches (seed + rank), value = global samples / s.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run does only what that line's headline figure needs: it sets up (model, resident
+batches, GEMM plans, graph captures, the eager-vs-graph choice), warms up, times the K steps, writes the last step's
+outputs when --dump-outputs DIR is given, and prints the line.  With --full the line also carries
   "roofline":     the dominant hand-written kernel, timed live with HIP events on the launching stream;
   "cpu_baseline": the CPU oracle (oracle/bevbert_ref.py, a restatement pinned to the reference) doing the same
                   fwd+bwd+AdamW on the host cores, on a bounded sample (rank 0, N = 1 only);
-  "kernels":      per-kernel-class time of one profiled step of each task (custom kernels vs library GEMMs).
+  "kernels":      per-kernel-class time of one profiled step of each task (custom kernels vs library GEMMs);
+and the forward-only timing, the whole-task-cycle figure, the live-loader ("sustained") blocks, the side
+configurations and, on several ranks, the "rccl" block (each can still be skipped with its --no-* option).
 """
 import argparse
 import json
@@ -108,7 +112,17 @@ def parse():
                     help="how the step is issued: eager (~700 launches from Python), graph (hipGraph replay), or auto = time "
                          "both in the untimed preparation and keep the faster one (BEVBERT_GRAPHS=0/1 in the environment "
                          "forces eager / graph as well)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline figure (kernel pass and rooflines, forward timing, "
+                         "whole task cycles, live-loader blocks, CPU baseline, side configurations, the rccl block, "
+                         "BEVBERT_STEP_EVENTS); a plain run only sets up, warms up and times the steps")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32): its loss and "
+                         "a fixed, seeded sample of the parameters it updated")
+    a = ap.parse_args()
+    if not a.full:              # the optional blocks belong to --full
+        a.no_cpu_baseline = a.no_kernel_pass = a.no_side = a.no_fwd = a.no_stream = True
+    return a
 
 
 def algorithmic_work(key, args, esize):
@@ -302,6 +316,25 @@ def compact_line(out, detail_path=None):
     return line
 
 
+DUMP_SAMPLE = 1 << 21       # sampled positions of the parameter arena: 8 MB of float32
+
+
+def dump_outputs(out_dir, loss, arena):
+    """--dump-outputs: what the caller of the last timed step receives -- its loss and the parameters it updated (a fixed,
+    seeded sample of positions of the flat fp32 master arena) -- as float32 .npy files, so that two builds run with the
+    same arguments can be compared output for output.  The gradient arena is the step's intermediate, not an output: two
+    runs on one box agree bit for bit, but between two boxes running the same build it differed by ~10 % (the
+    parameters by ~1e-6, the loss by ~4e-4)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    idx = np.unique(np.random.default_rng(20261015).integers(0, arena.numel, DUMP_SAMPLE))
+    idx = torch.from_numpy(idx).to(arena.params.device)
+    torch.cuda.synchronize()
+    for name, t in (("loss", loss.reshape(())), ("params_sample", arena.params[idx])):
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+    log(f"outputs of the last timed step -> {out_dir}")
+
+
 def main():
     a = parse()
     # watchdog: a stalled run (a collective that never completes, a wedged queue) dumps every thread's Python stack to
@@ -464,8 +497,10 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     value = a.steps * a.batch * world / dt
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, losses[-1], arena)
     resident_events = None
-    if os.environ.get("BEVBERT_STEP_EVENTS") == "1":        # diagnosis (after the timed region): device time per step + gaps
+    if a.full and os.environ.get("BEVBERT_STEP_EVENTS") == "1":     # diagnosis (after the timed region): device time per step + gaps
         marks = []
         for _ in range(3 * len(cycle)):
             t = cycle[counter[0] % len(cycle)]
@@ -477,7 +512,7 @@ def main():
         resident_events = _step_event_digest(marks)
         log(f"step events, resident: {resident_events}")
     whole = None
-    if a.steps % len(cycle):
+    if a.full and a.steps % len(cycle):
         # K is not a whole number of 11-step task cycles (the driver's --steps 20): the K steps above are the contract's
         # timed region; a second region of ceil(K / 11) whole cycles, continuing the same walk from a cycle boundary, gives
         # the figure for the exact 5:5:1 task mix next to it
@@ -567,7 +602,7 @@ def main():
         out["fwd_ms_per_batch"] = fwd
     if rank == 0 and a.no_fwd:
         pass
-    if world > 1 or force:
+    if a.full and (world > 1 or force):
         # what the exchange moves, and how long it takes alone (all ranks take part; rank 0 reports)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -793,8 +828,8 @@ def main():
             log("sustained throughput with a live loader, ragged batches (child process)")
             try:
                 import subprocess
-                cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--ragged", "--steps", "22", "--warmup", "11", "--no-side",
-                       "--no-cpu-baseline", "--no-kernel-pass", "--no-fwd", "--config", a.config, "--batch", str(a.batch),
+                cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--ragged", "--steps", "22", "--warmup", "11",
+                       "--no-side", "--no-cpu-baseline", "--no-kernel-pass", "--no-fwd", "--config", a.config, "--batch", str(a.batch),
                        "--txt-len", str(a.txt_len), "--txt-len-min", str(a.txt_len_min), "--stream-steps", str(a.stream_steps),
                        "--dtype", a.dtype, "--residual", a.residual]
                 child_detail = os.path.splitext(a.detail)[0] + "_ragged_child.json"

@@ -10,7 +10,7 @@ OUT=$ROOT/gpurun_out/prof_${TAG}_kernel_pass
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 timeout 600 rocprofv3 --kernel-trace --output-format csv -d "$OUT/trace" -o bench -- python $ROOT/bench.py --steps 11 --warmup 11 \
-  --no-cpu-baseline --no-stream --no-side --no-fwd --detail $OUT/bench_detail.json > "$OUT/bench_line.json" 2> "$OUT/log.txt"
+  --full --no-cpu-baseline --no-stream --no-side --no-fwd --detail $OUT/bench_detail.json > "$OUT/bench_line.json" 2> "$OUT/log.txt"
 python "$ROOT/scripts/summarize_trace.py" "$OUT/trace" 3 > "$OUT/kernel_pass_steps.txt" 2>&1
 rm -rf "$OUT/trace"
 python - "$OUT" <<'PY'

@@ -3,7 +3,7 @@
 #   parts (default: all, in this order):
 #     tests    every -m gpu test (+ the bf16 error ratios the model tests log)
 #     smoke    __graft_entry__.smoke()
-#     bench    the default `python bench.py` line (resident + sustained + ragged sustained + side configs + cpu baseline)
+#     bench    the `python bench.py --full` line (resident + sustained + ragged sustained + side configs + cpu baseline)
 #     profile  rocprofv3 --kernel-trace --stats of the bench command, per-step / per-shape tables (summarize_trace.py)
 #     sq       SQ counters of the attention kernels at the BEV self-attention shape (separate --pmc passes)
 #     traffic  FETCH_SIZE / WRITE_SIZE per launch of every hand-written HBM-bound kernel against its algorithmic bytes
@@ -42,7 +42,7 @@ for P in $PARTS; do
     smoke)
       timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -5 > ${O}_smoke.log; tail -1 ${O}_smoke.log ;;
     bench)
-      timeout 1200 python bench.py > ${O}_bench.json 2> ${O}_bench.err || tail -5 ${O}_bench.err
+      timeout 1200 python bench.py --full > ${O}_bench.json 2> ${O}_bench.err || tail -5 ${O}_bench.err
       line ${O}_bench.json ;;
     profile)
       bash scripts/gpu_profile.sh ${T} --no-stream --no-side --no-fwd > /dev/null 2>&1
@@ -53,7 +53,7 @@ for P in $PARTS; do
     traffic)
       bash scripts/gpu_pmc_all.sh ${T} 2>&1 | tail -40 ;;
     modes)
-      BEVBERT_FORCE_COLLECTIVES=1 timeout 600 python bench.py --no-side --no-cpu-baseline --no-stream > ${O}_bench_forced_collectives.json 2> ${O}_bench_forced.err; line ${O}_bench_forced_collectives.json ;;
+      BEVBERT_FORCE_COLLECTIVES=1 timeout 600 python bench.py --full --no-side --no-cpu-baseline --no-stream > ${O}_bench_forced_collectives.json 2> ${O}_bench_forced.err; line ${O}_bench_forced_collectives.json ;;
     nav)
       rm -f ${O}_nav.jsonl
       for args in "--map device" "--map device --feedback" "--map host" "--map host --feedback" \

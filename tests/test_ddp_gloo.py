@@ -1,6 +1,7 @@
 """world_size-2 gloo test (CPU) of the data-parallel gradient exchange: the in-place two-phase arena all-reduce used by
 PretrainTrainer gives, together with the 1/world pre-scale, the gradient of the global batch; ranks draw disjoint
 batches and agree on the task sequence without a collective."""
+import gc
 import os
 import socket
 
@@ -215,6 +216,11 @@ def _toy_run(rank, world, port, out):
     if rank == 0:
         torch.save({"a": model.a.detach().clone(), "b": model.b.detach().clone()}, out)
     if world > 1:
+        # ArenaDataParallel leaves the process group on the arena (allreduce_group), and the arena sits in reference
+        # cycles with its module: free them while the group is up -- left to the interpreter's exit, the group's C++
+        # side is torn down last and the rank can abort there ("terminate called without an active exception")
+        del net, model, opt
+        gc.collect()
         dist.destroy_process_group()
 
 
@@ -263,6 +269,8 @@ def _union_run(rank, world, port, out):
         opt.step()
         opt.zero_grad()
     torch.save({"extra": model.extra.detach().clone(), "a": model.a.detach().clone()}, out + f".{rank}")
+    del net, model, opt                                # see _toy_run: the group must not outlive the run
+    gc.collect()
     dist.destroy_process_group()
 
 

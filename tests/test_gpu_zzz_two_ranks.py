@@ -158,7 +158,7 @@ def test_bench_multi_rank_path_rehearsed_with_two_ranks_on_one_gpu():
     detail = os.path.join(root, "gpurun_out", "bench_detail_rehearsal.json")
     os.makedirs(os.path.dirname(detail), exist_ok=True)
     pr = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "11", "--warmup", "2",
-                         "--launch", "eager", "--no-side", "--no-stream", "--no-cpu-baseline", "--no-fwd", "--no-kernel-pass",
+                         "--full", "--launch", "eager", "--no-side", "--no-stream", "--no-cpu-baseline", "--no-fwd", "--no-kernel-pass",
                          "--detail", detail], capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert pr.returncode == 0, pr.stderr[-2000:]
     line = pr.stdout.strip().splitlines()[-1]
