@@ -577,6 +577,59 @@ def test_graph_bias_shared_by_the_layers_of_an_encoder(ops, dtype):
     assert torch.equal(run(), g)                           # fixed summation order
 
 
+@pytest.mark.parametrize("routes,in_arena", [(("attn", "attn", "attn"), True), (("attn", "torch", "none"), True),
+                                             (("torch", "torch", "none"), True), (("clone", "none", "attn"), True),
+                                             (("attn", "torch", "attn"), False)])
+def test_graph_bias_gradient_by_every_route(ops, routes, in_arena):
+    """d sprel_linear.weight / .bias of ops.graph_bias whatever way the gradient reaches the per-layer views: through a
+    slot-aware attention backward (the holder), through a plain torch expression, through attention on a copy of the view
+    (no slot), not at all -- into the arena, or returned to autograd for plain parameters -- against the fp64 composition."""
+    from vln_bevbert_amd.arena import ParamArena
+    B, G, nh = 5, 20, 12
+    g = torch.Generator(device="cpu").manual_seed(8)
+    lin = torch.nn.Linear(1, 1)
+    with torch.no_grad():
+        lin.weight.fill_(0.7)
+        lin.bias.fill_(-0.2)
+    arena = ParamArena(lin, DEV, torch.float32) if in_arena else None
+    if not in_arena:
+        lin.to(DEV)
+    dists = (torch.rand(B, G, G, generator=g) * 3).to(DEV)
+    km = torch.zeros(B, G, device=DEV)
+    km[1, 15:] = -10000.0
+    qkv = [tuple(torch.randn(B, G, 768, generator=g).to(DEV) for _ in range(3)) for _ in routes]
+    do = [torch.randn(B, G, 768, generator=g).to(DEV) for _ in routes]
+    e = [torch.randn(B, G, G, generator=g).to(DEV) for _ in routes]
+
+    def consume(bias, i, route, attn):
+        if route in ("attn", "clone"):
+            q, k, v = qkv[i]
+            return (attn(q, k, v, km, bias if route == "attn" else bias.clone(), nh) * do[i]).sum()
+        return (bias * e[i]).sum() if route == "torch" else 0
+
+    bs = ops.graph_bias(dists, lin.weight, lin.bias, len(routes), nh)
+    tot = sum(consume(b_, i, r, lambda *a: ops.attention(*a, impl=1)) for i, (b_, r) in enumerate(zip(bs, routes)))
+    tot.backward()
+    torch.cuda.synchronize()
+    if in_arena:
+        arena.sync()
+        got = [float(arena.grads[arena.slices[n][0]]) for n in ("weight", "bias")]
+    else:
+        assert lin.weight.grad is not None and lin.bias.grad is not None, "no gradient for plain parameters"
+        got = [float(lin.weight.grad), float(lin.bias.grad)]
+    wr = torch.tensor(0.7, dtype=torch.float64, device=DEV, requires_grad=True)
+    br = torch.tensor(-0.2, dtype=torch.float64, device=DEV, requires_grad=True)
+    ref_bias = dists.double() * wr + br
+    qkv = [tuple(t.double() for t in x) for x in qkv]
+    do, e = [t.double() for t in do], [t.double() for t in e]
+    ref = sum(consume(ref_bias, i, r, lambda *a: _attn_ref(*a[:3], a[3].double(), a[4], nh))
+              for i, r in enumerate(routes))
+    ref.backward()
+    want = [float(wr.grad), float(br.grad)]
+    scale = max(1.0, abs(want[0]), abs(want[1]))
+    assert abs(got[0] - want[0]) < 1e-3 * scale and abs(got[1] - want[1]) < 1e-3 * scale, (routes, got, want)
+
+
 @pytest.mark.parametrize("dtype,fuse", [(torch.float32, True), (torch.float32, False), (torch.bfloat16, True)])
 def test_fused_sap_loss_tail_matches_the_torch_composition(ops, dtype, fuse):
     """ops.sap_loss == pretrain_cmt.forward_sap's tail written with torch ops (masked fills, fuse_sap_logits, three
@@ -1009,6 +1062,61 @@ def test_attention_full_size_softmax_properties(ops):
     o = ops.attention(q, k, v, None, None, nh)
     ref = _attn_ref(q[:2].float(), k[:2].float(), v[:2].float(), None, None, nh)
     assert float((o[:2].float() - ref).abs().max()) < 1e-2 * float(ref.abs().max())
+
+
+@pytest.mark.parametrize("Lq,Lk,mode,mk", [(441, 441, "self", None), (441, 80, "cross", "neg"), (80, 441, "sep", None),
+                                           (80, 80, "self", "neg")])
+def test_attention_at_the_benched_batch_with_dropout(ops, Lq, Lk, mode, mk):
+    """B = 64 with dropout through the entry points the model calls (packed QKV, packed KV, separate operands), forward
+    and backward, against the fp32 reference under the exported mask.  At 441 x 441 the default dispatch must take the
+    benched kernels: the persistent forward (attn_fwd4, chosen only when the items fill two rounds of CUs) and attn_bwd3."""
+    B, p, dtype = 64, 0.1, torch.bfloat16
+    q, k, v, km, _, nh = _make_attn_inputs(B, Lq, Lk, mk, False, dtype, seed=Lq + 3 * Lk)
+    do = torch.randn(B, Lq, 768, device=DEV, generator=torch.Generator(device=DEV).manual_seed(Lq)).to(dtype)
+    ops.RT.new_step(2024 + Lq + Lk)
+    off = ops.RT.offset
+    # the traced call records the kernel each launch took (the backward runs on autograd's device thread, where the
+    # library's last-path record of this thread is not visible)
+    ops.RT.trace, ops.RT.paths = {}, {}
+    try:
+        if mode == "self":
+            a = torch.cat([q, k, v], -1).requires_grad_(True)
+            o = ops.attention_self(a, km, None, nh, p, training=True)
+        elif mode == "cross":
+            a, kv = q.clone().requires_grad_(True), torch.cat([k, v], -1).requires_grad_(True)
+            o = ops.attention_cross(a, kv, km, nh, p, training=True)
+        else:
+            a, ki, vi = (t.clone().requires_grad_(True) for t in (q, k, v))
+            o = ops.attention(a, ki, vi, km, None, nh, p, training=True)
+        o.backward(do)
+        torch.cuda.synchronize()
+        paths = sorted(k_.split(" -> ")[1] for k_ in ops.RT.paths)
+    finally:
+        ops.RT.trace, ops.RT.paths = None, {}
+    print(f"\nB=64 {Lq}x{Lk} {mode}: {paths}")
+    if Lq == Lk == 441:
+        assert paths == ["attn_bwd3", "attn_fwd4"], paths
+    if mode == "self":
+        dq, dk, dv = a.grad.split(768, -1)
+    elif mode == "cross":
+        dq, (dk, dv) = a.grad, kv.grad.split(768, -1)
+    else:
+        dq, dk, dv = a.grad, ki.grad, vi.grad
+    o = o.detach().float()
+    del a
+    Lk2 = (Lk + 1) // 2 * 2            # the kernels index dropout elements with the key count rounded up to even
+    keep = ops.dropout_keep_mask(B * nh * Lq * Lk2, p, ops.RT.seed, off, DEV).view(B, nh, Lq, Lk2)[..., :Lk]
+    qr, kr, vr = (t.float().requires_grad_(True) for t in (q, k, v))
+    orf = _attn_ref(qr, kr, vr, km, None, nh, keep, p)
+    scale = max(1.0, float(orf.abs().max()))
+    err = float((o - orf.detach()).abs().max()) / scale
+    assert err < 1.5e-2, err
+    orf.backward(do.float())
+    errs = {n: rel_err(x, r.grad) for n, x, r in (("dq", dq, qr), ("dk", dk, kr), ("dv", dv, vr))}
+    print(f"worst: forward {err:.3e} " + " ".join(f"{n} {x:.3e}" for n, x in errs.items()))
+    assert max(errs.values()) < 3e-2, errs
+    del orf, keep, qr, kr, vr
+    torch.cuda.empty_cache()
 
 
 # ----------------------------------------------------------------------------- K7 optimiser

@@ -55,6 +55,15 @@ def test_invalid_arguments_are_rejected_without_a_gpu():
     strides = (ctypes.c_int64 * 8)(*([768] * 8))
     rc = l.bevbert_attn_fwd(None, None, None, None, None, None, None, strides, 1, 12, 4, 4, 32, 0.125, 1, 0, 0.0, 0, 0, None, 0, None)
     assert rc == -1 and b"head_dim" in l.bevbert_last_error()
+    # the fp32-residual LayerNorm has kernels for H = 256, 512, 768 and 1024 only; H <= 0 must not reach a launch
+    for H in (0, -256, 1280):
+        rc = l.bevbert_layernorm_res32_fwd(None, None, None, 0, None, None, None, None, None, None, None, 1, H, 1e-12,
+                                           0.0, 0, 0, None)
+        assert rc == -1 and b"must be 256, 512, 768 or 1024" in l.bevbert_last_error(), (H, rc)
+        dy16 = ctypes.c_uint16(0)           # a non-null output gradient, so that the shape check is the one that fires
+        rc = l.bevbert_layernorm_res32_bwd(ctypes.addressof(dy16), None, None, None, None, None, None, None, None, None,
+                                           None, None, 1, H, 0.0, 0, 0, 0, 0, None)
+        assert rc == -1 and b"must be 256, 512, 768 or 1024" in l.bevbert_last_error(), (H, rc)
 
 
 def test_cpu_tensors_fail_loudly():

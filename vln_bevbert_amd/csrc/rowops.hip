@@ -1307,7 +1307,7 @@ BEVBERT_API int bevbert_layernorm_res32_fwd(const void* x, const float* bias, co
                                             const float* gamma, const float* beta, void* y16, float* y32, float* z32,
                                             float* mean, float* rstd, int rows, int H, float eps, float drop_p,
                                             uint64_t seed, uint64_t offset, hipStream_t stream) {
-  BB_REQUIRE(rows >= 0 && H % 256 == 0 && H / 256 <= 4, "layernorm_res32_fwd: H=%d must be 256, 512, 768 or 1024", H);
+  BB_REQUIRE(rows >= 0 && H >= 256 && H % 256 == 0 && H / 256 <= 4, "layernorm_res32_fwd: H=%d must be 256, 512, 768 or 1024", H);
   BB_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "layernorm_res32_fwd: dropout p=%f", drop_p);
   BB_REQUIRE(residual == nullptr || residual_dtype == BB_F32 || residual_dtype == BB_BF16, "layernorm_res32_fwd: residual dtype %d", residual_dtype);
   if (rows == 0) return BB_OK;
@@ -1337,7 +1337,7 @@ BEVBERT_API int bevbert_layernorm_res32_bwd(const void* dy16, const float* dy32,
                                             uint64_t seed, uint64_t offset, int accumulate, int dz_dtype,
                                             hipStream_t stream) {
   BB_REQUIRE(dz_dtype == BB_F32 || dz_dtype == BB_BF16, "layernorm_res32_bwd: dz dtype %d (fp32 or bf16)", dz_dtype);
-  BB_REQUIRE(H % 256 == 0 && H / 256 <= 4, "layernorm_res32_bwd: H=%d must be 256, 512, 768 or 1024", H);
+  BB_REQUIRE(H >= 256 && H % 256 == 0 && H / 256 <= 4, "layernorm_res32_bwd: H=%d must be 256, 512, 768 or 1024", H);
   BB_REQUIRE(dy16 != nullptr || dy32 != nullptr, "layernorm_res32_bwd: no output gradient");
   if (rows <= 0) return BB_OK;
   const int nb = partial_blocks(rows, 16);

@@ -122,7 +122,9 @@ class _BiasGradHolder:
         if self.buf is None:
             self.buf = torch.empty(self.layers, B, self.nh, G, G, dtype=torch.float32, device=device)
             call("bevbert_zero", ptr(self.buf), self.buf.numel() * 4, stream())
-            self.dummy = torch.empty((), dtype=torch.float32, device=device).expand(B, G, G)    # never read: a shape for autograd
+            # the gradient _Attention hands autograd in place of the one it left here: zeros, because autograd adds it to
+            # the gradients other consumers of the same view produce, which _GraphBias.backward then reduces as they come
+            self.dummy = torch.zeros((), dtype=torch.float32, device=device).expand(B, G, G)
         return self.buf[i]
 
 
@@ -144,18 +146,34 @@ class _GraphBias(torch.autograd.Function):
         (dists,) = ctx.saved_tensors
         weight, bias = ctx.params
         h = ctx.holder
-        if h.buf is None:
+        # gradients that reached a view some other way than a slot-aware attention backward (another consumer, a view
+        # without its slot, a cross-shaped attention): reduced by the same kernel, after the holder, in view order
+        dummy = h.dummy.data_ptr() if h.dummy is not None else None
+        extra = [g for g in grads if g is not None and g.data_ptr() != dummy]
+        if h.buf is None and not extra:
             return None, None, None, None, None
-        sinks = []
-        for p in (weight, bias):
+        B, G = dists.shape[0], dists.shape[-1]
+        sinks, tmp = [], None
+        for i, p in enumerate((weight, bias)):
             s = _sink(p) if p.requires_grad else None
             if s is not None:
                 _mark_touched(p)
+            elif p.requires_grad:             # a plain parameter: reduced into a temporary, returned to autograd
+                if tmp is None:
+                    tmp = torch.zeros(2, dtype=torch.float32, device=dists.device)
+                s = tmp[i:i + 1]
             sinks.append(s)
-        B, G = dists.shape[0], dists.shape[-1]
         ws = torch.empty(1024, dtype=torch.float32, device=dists.device)
-        call("bevbert_graph_bias_bwd", ptr(h.buf), ptr(dists), h.layers, B, h.nh, G, ptr(sinks[0]), ptr(sinks[1]), ptr(ws), stream())
-        return None, None, None, None, None
+        if h.buf is not None:
+            call("bevbert_graph_bias_bwd", ptr(h.buf), ptr(dists), h.layers, B, h.nh, G, ptr(sinks[0]), ptr(sinks[1]),
+                 ptr(ws), stream())
+        if extra:
+            st = torch.stack([g.to(torch.float32) for g in extra])
+            call("bevbert_graph_bias_bwd", ptr(st), ptr(dists), len(extra), B, 1, G, ptr(sinks[0]), ptr(sinks[1]),
+                 ptr(ws), stream())
+        gw, gb = (None if tmp is None or _sink(p) is not None or not p.requires_grad else s.view(p.shape).to(p.dtype)
+                  for p, s in zip((weight, bias), sinks))
+        return None, gw, gb, None, None
 
 
 def graph_bias(dists, weight, bias, layers, nh):
