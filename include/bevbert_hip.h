@@ -447,6 +447,67 @@ int bevbert_gm_embed_update(const bevbert_gm_state* st, void* embed_sum, float* 
 int bevbert_gm_node_embeds(const bevbert_gm_state* st, const void* embed_sum, const float* embed_cnt, const int* node,
                            const int* cnt, int G, int H, int dtype, void* out, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Fine-tune supervision (since 0.1.2; entry points added, ABI otherwise unchanged).  Replaces map_nav_src/r2r/agent.py:371-417
+ * (_teacher_action_r4r), :523-534,559-612 (stop scores, feedback modes, stop rule, stop-node pick), agent_base.py:148 (the
+ * IL criterion) and r2r/env.py:309-378 + r2r/eval_utils.py (_eval_item, eval_metrics, cal_dtw, cal_cls).
+ * Graph tables (vln_bevbert_amd/nav_expert.py ScanGraphs): dist (S,N,N) f64 = networkx all-pairs Dijkstra lengths (inf =
+ * unreachable / padding), pred (S,N,N) i16 = predecessor of v on networkx's path from u (-1 = none).  Node ids are scan
+ * indices; ids outside [0, N) read as unreachable.  No entry synchronises with the host. */
+
+/* Expert targets (B) i64: policy 0 = imitation (slot of gt[t+1], 0 at the last gt step), 1 = spl (first strict minimum
+ * of d[vp][goal] + d[cur][vp]), 2 = ndtw (first strict minimum of -nDTW(traj ++ path(cur, vp)[1:], gt, 3.0)); slots j >= 1
+ * of cand (B,C) (-1 = padding) not flagged in visited (B,C) u8 (may be NULL); 0 when cur is the goal; -100 for ended
+ * samples and when every slot is excluded.  gt (B,Lg) + gt_len (B); traj (B,Lt) + traj_len (B) (ndtw only,
+ * Lt + N <= 1023). */
+int bevbert_nav_expert(const double* dist, const int16_t* pred, int N, int S, const int* scan, const int* cur,
+                       const int* cand, const uint8_t* visited, const uint8_t* ended, const int* gt, const int* gt_len,
+                       int Lg, const int* traj, const int* traj_len, int Lt, int B, int C, int t, int policy, int64_t* out,
+                       hipStream_t stream);
+
+/* One navigation step's decision for B samples from logits (B,C) (dtype 0/1, -inf = masked).  feedback 0 = teacher
+ * (targets), 1 = argmax, 2 = sample (inverse CDF of a uniform draw), 3 = expl_sample (first max of the logits = of the probabilities; with
+ * probability P(u > expl_max_ratio) a uniform pick among masks (B,C) u8).  Draws hash (seed, t) with the step salt.
+ * Live samples store p[0] as the stop score of node cur in stop_scores (B,N) (first-insertion order in stop_order (B,N),
+ * n_stop (B)).  Stop: teacher / sample at goal[b], else a == 0; also ended, no_vp_left (may be NULL), t == max_len - 1.
+ * Outputs: a_t (B) i64, node (B) = cand[b, a], or -1 when the sample does not move (the reference's None action);
+ * just_ended (B) u8 = the sample stops this step (stop rule, no_vp_left, last step) and gets a stop-node pick:
+ * stop_node (B) = first max of its stop scores (else -1); entropy (B) f32, rand (B) f32 (the uniform draw used).
+ * ended[b] is set for every node == -1, as agent.py:615 does -- also for a live sample whose slot has no viewpoint
+ * (slot 0 away from the goal in teacher / sample mode), which ends in place without a stop-node pick.  Stops are
+ * signalled by just_ended, not by node == -1. */
+int bevbert_nav_action(const void* logits, int dtype, int B, int C, int feedback, int t, int max_len,
+                       const int64_t* targets, const int* cand, const int* cur, const int* goal, uint8_t* ended,
+                       const uint8_t* no_vp_left, const uint8_t* masks, float* stop_scores, int* stop_order, int* n_stop,
+                       int N, float expl_max_ratio, uint32_t seed, int64_t* a_t, int* node, uint8_t* just_ended,
+                       int* stop_node, float* entropy, float* rand, hipStream_t stream);
+
+/* CrossEntropyLoss(ignore_index = ignore, reduction='sum') of logits (B,C) (dtype 0/1): out (2B+1) f32 = [lse (B) |
+ * per-row loss (B) | sum in row order]; targets equal to ignore or outside [0, C) contribute 0.  bwd: dlogits (B,C) =
+ * dloss[0] * (softmax - onehot), 0 on ignored rows. */
+int bevbert_nav_ce_fwd(const void* logits, const int64_t* target, float* out, int B, int C, int ignore, int dtype,
+                       hipStream_t stream);
+int bevbert_nav_ce_bwd(const void* logits, const int64_t* target, const float* out, const float* dloss, void* dlogits,
+                       int B, int C, int ignore, int dtype, hipStream_t stream);
+
+/* Trajectory record (graph_utils.py:85-93 FloydGraph.path, agent.py:418-434 / :598-599 the appends): for every b with
+ * live[b], n_seg[b] += 1 and traj[b, traj_len[b]..] += the nodes of path(from[b], to[b]) after from[b] (none when equal),
+ * expanded from the agent map's next-hop table point (B,Nm,Nm) (-1 = direct edge; bevbert_gm_state.point) and written as
+ * node_scan[b, node] (B,Nm) scan indices.  A full record or a table that is not a next-hop table sets *overflow (read it
+ * once per episode). */
+int bevbert_nav_traj_append(const int* point, int Nm, const int* node_scan, const int* from, const int* to,
+                            const uint8_t* live, int* traj, int* traj_len, int Lt, int* n_seg, int* overflow, int B,
+                            hipStream_t stream);
+
+/* _eval_item of B finished trajectories, f64: path (B,Lp) = sum(pred_path, []) + path_len (B), action_steps (B) =
+ * len(pred_path) - 1, gt (B,Lg) + gt_len (B), margin = ERROR_MARGIN (3.0).  items (B,12): nav_error, oracle_error,
+ * action_steps, trajectory_steps, trajectory_lengths, success, spl, oracle_success, DTW, nDTW, SDTW, CLS.  avg (11) or
+ * NULL: eval_metrics' means (action_steps, steps, lengths, nav_error, oracle_error, sr, oracle_sr, spl, nDTW, SDTW, CLS;
+ * the last six x100), summed in sample order.  Lp < 1024.  A scan index outside [0, S) gives a row of NaN. */
+int bevbert_nav_metrics(const double* dist, int N, int S, const int* scan, const int* path, const int* path_len, int Lp,
+                        const int* action_steps, const int* gt, const int* gt_len, int Lg, int B, double margin,
+                        double* items, double* avg, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
