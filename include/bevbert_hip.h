@@ -508,6 +508,45 @@ int bevbert_nav_metrics(const double* dist, int N, int S, const int* scan, const
                         const int* action_steps, const int* gt, const int* gt_len, int Lg, int B, double margin,
                         double* items, double* avg, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Candidate waypoint prediction of the continuous-environment agent (since 0.2.0; entry points added, ABI otherwise
+ * unchanged).  Replaces bevbert_ce/vlnce_baselines/waypoint_pred/transformer/waypoint_bert.py:66-86 (the ring-masked
+ * self-attention of BinaryDistPredictor_TRM), models/Policy_ViewSelection_BEV.py:196-321 (mode 'waypoint' after the
+ * predictor: softmax, waypoint_pred/utils.py nms, the waypoint_aug draw, candidate features, pooling and re-ordering)
+ * and ss_trainer_BEV.py:347-384 (_vp_feature_variable).  Forward only, no atomics, fixed output shapes (K_MAX = 5
+ * candidates, L = 17 panorama rows); no entry synchronises with the host, so the stage can sit in a captured step.
+ * The reference's behaviour is kept as it executes, quirks included: they are listed in csrc/waypoint.hip. */
+
+/* Self-attention over the ring of 12 views: qkv (B,12,3*nh*64) packed [q | k | v] (dtype 0/1), out (B,12,nh*64).  Query i
+ * attends to keys i-1, i, i+1 (mod 12); the reference's additive -10000 on the other nine keys underflows to an exact 0
+ * weight in fp32, so this is the same function.  No dropout, no backward (the predictor is frozen, always eval). */
+int bevbert_wp_ring_attn(const void* qkv, void* out, int B, int nh, float scale, int dtype, hipStream_t stream);
+
+/* logits (B,12,120) f32: the classifier output BEFORE the predictor's roll by HEATMAP_OFFSET = 5 (row 10*img + k of the
+ * (120,12) view is angle 10*img + k - 5).  Per sample: softmax over the 1 440 cells of the rolled map -> heat (B,120,12);
+ * one wrap row on either side; 5 rounds of arg-max (first index wins ties) + suppression, sigma = (7, 5); the surviving
+ * picks of rows 1..120 in row-major order are the candidates: cand_count (B).  in_train != 0 (waypoint_aug): candidate k
+ * is replaced by an inverse-CDF draw over the 120 cells of its image's region, region_probs (B,5,120) (0 for k >=
+ * cand_count), with the uniform rand (B,5) = 24 bits of hash((seed, t), step salt, 8 b + k) -- all five are written, the
+ * first cand_count are used.  Outputs, padding -1 / 0: cand_angle_idx, cand_dist_idx, cand_img_idx (counter-clockwise)
+ * (B,5) i32; cand_angle_fts (B,5,4) = [sin, cos, 0, 1] of the clockwise angle; cand_angles (B,5) counter-clockwise
+ * radians; cand_distances (B,5) = (dist_idx + 1) / 4.  region_probs and rand may be NULL when in_train == 0. */
+int bevbert_wp_candidates(const float* logits, int B, int in_train, uint32_t seed, int t, int* cand_count,
+                          int* cand_angle_idx, int* cand_dist_idx, int* cand_img_idx, float* cand_angle_fts,
+                          float* cand_angles, float* cand_distances, float* region_probs, float* heat, float* rand,
+                          hipStream_t stream);
+
+/* rgb_embeds (B*12,512), depth_embeds (B*12,128,4,4) in the predictor's clockwise view order (dtype 0/1, outputs alike);
+ * pano_angle_fts (12,4) f32 = the angle features of the counter-clockwise views.  pano_rgb (B,12,512), pano_depth
+ * (B,12,128) (4 x 4 mean): counter-clockwise view i = input view (12 - i) % 12.  Panorama-encoder inputs padded to L = 17:
+ * rgb_fts (B,17,512), dep_fts (B,17,128), loc_fts (B,17,4) f32, nav_types (B,17) i64, view_lens (B) i64; rows = the
+ * candidates in order (view cand_img_idx, own angle feature, type 1), the views no candidate points into in ascending
+ * index (type 0), zeros. */
+int bevbert_wp_pano_inputs(const void* rgb_embeds, const void* depth_embeds, int dtype, int B, const int* cand_count,
+                           const int* cand_img_idx, const float* cand_angle_fts, const float* pano_angle_fts,
+                           void* pano_rgb, void* pano_depth, void* rgb_fts, void* dep_fts, float* loc_fts,
+                           int64_t* nav_types, int64_t* view_lens, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,6 +3,7 @@
 Public surface (mirrors the reference's module boundary):
     GlocalTextPathCMT, GlocalTextPathCMTPreTraining      (pretrain_src/model/{vilmodel,pretrain_cmt}.py)
     GlocalTextPathNavCMT, VLNBert                        (map_nav_src/models/{vilmodel,model}.py)
+    WaypointPredictor, waypoint_step, to_reference       (bevbert_ce/vlnce_baselines: waypoint_pred/TRM_net.py + mode 'waypoint')
     BevBertConfig, ParamArena, PretrainTrainer, synthetic batches
 Compute goes through libbevbert_hip.so (include/bevbert_hip.h); there is no CPU / eager fallback.
 """
@@ -29,6 +30,7 @@ def __getattr__(name):
         "GlocalTextPathCMT": "vilmodel", "GlocalTextPathCMTPreTraining": "pretrain_cmt",
         "GlocalTextPathNavCMT": "nav_model", "VLNBert": "nav_model", "ParamArena": "arena",
         "PretrainTrainer": "train", "GradReducer": "train",
+        "WaypointPredictor": "waypoint", "waypoint_step": "waypoint", "to_reference": "waypoint",
     }
     if name in table:
         return getattr(importlib.import_module(f"{__name__}.{table[name]}"), name)

@@ -37,7 +37,7 @@ BEVBERT_API int bevbert_zero(void* p, int64_t bytes, hipStream_t stream) {
   return BB_OK;
 }
 
-BEVBERT_API int bevbert_version(void) { return 112; }  // 0.1.2: fine-tune supervision entries (nav_expert.hip)
+BEVBERT_API int bevbert_version(void) { return 200; }  // 0.2.0: candidate waypoint prediction entries (waypoint.hip)
 
 static const uint32_t* g_step_salt = nullptr;
 const uint32_t* bb_step_salt() { return g_step_salt; }
