@@ -46,6 +46,13 @@ const char* bevbert_arch(void);
  * dispatched to ("attn_fwd4", "attn_bwd3", "attn_short_fwd", ...; "" before the first call).  The choice depends on
  * shape, dtype, dropout and the BEVBERT_ATTN_* environment knobs; tests and bench.py use this to prove which path ran. */
 const char* bevbert_attn_last_path(int backward);
+/* The same choice without a call: the kernel bevbert_attn_fwd (backward = 0) / bevbert_attn_bwd (backward = 1) would take
+ * for this shape with suitably aligned operands, under the BEVBERT_ATTN_* knobs the environment holds right now.  has_* /
+ * want_dbias say which optional pointers the call would pass; ncu is the CU count the occupancy rule of the persistent
+ * forward plans for (<= 0: this device's).  Launches nothing, and with ncu > 0 touches no device; "" for a dtype / impl
+ * pair the calls reject. */
+const char* bevbert_attn_plan(int B, int nh, int Lq, int Lk, int dtype, int impl, int has_key_mask, int has_bias,
+                              float drop_p, int has_bits, int bits_ready, int want_dbias, int ncu, int backward);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * K1  lift + BEV binning + deterministic scatter-mean.
@@ -108,6 +115,9 @@ int bevbert_attn_bwd(const void* q, const void* k, const void* v, const void* o,
 int64_t bevbert_attn_drop_bits_words(int B, int nh, int Lq, int Lk);
 int bevbert_attn_drop_bits(uint64_t* drop_bits, int B, int nh, int Lq, int Lk, float drop_p, uint64_t seed,
                            uint64_t offset, hipStream_t stream);
+/* 1: fill the workspace of this dropout site ahead of its forward (bevbert_attn_drop_bits, then bits_ready = 1); 0: pass
+ * bits_ready = 0 -- the forward hashes inline and leaves the bits behind for the backward (small score matrices). */
+int bevbert_attn_bits_ahead(int Lq, int Lk, int has_bias);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * K3  y = LayerNorm(dropout(x + bias) + residual).

@@ -47,7 +47,7 @@ def bench(B, Lq, Lk, p, iters, masked):
         km = torch.where(torch.arange(Lk, device=dev)[None] < lens[:, None], 0.0, -10000.0).float().contiguous()
     st = ops._strides(q, k, v, o)
     scale = 1.0 / math.sqrt(64)
-    big = Lq * Lk >= 32768 or Lk > 256               # ops_attention._Attention.forward's rule
+    big = bool(lib.load().bevbert_attn_bits_ahead(Lq, Lk, 0))    # the rule ops_attention._Attention.forward asks for
     bits = None
     if p > 0:
         bits = ops.attn_drop_bits(B, nh, Lq, Lk, p, 1, 0, dev) if big else \

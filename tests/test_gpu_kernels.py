@@ -937,6 +937,73 @@ def test_attention_persistent_forward_of_the_long_shapes(ops, B, Lq, Lk, mk, p, 
         assert rel_err(a, b_) < 3e-2, (name, rel_err(a, b_))       # the backward reads the log-sum-exp this forward wrote
 
 
+def test_attention_dispatch_runs_what_the_plan_says(ops, monkeypatch):
+    """bevbert_attn_plan against the calls it speaks for: the B = 2 rows of the dispatch table (tests/test_host_logic.py),
+    one of every kernel but the batch-dependent choice, issued as real forward + backward calls -- the recorded path is the
+    planned one, for this device's CU count.  Then a knob that used to be latched at the first call of a process, flipped
+    inside this one: BEVBERT_ATTN_BWD3=0 and unset on 300 x 290 select the two generations of the 7+1-wave backward, whose
+    gradients agree to the bound test_attention_persistent_forward_of_the_long_shapes holds two generations to."""
+    from tests.test_host_logic import ATTN_PLAN_ROWS, attn_plan
+    from vln_bevbert_amd import lib
+    from vln_bevbert_amd.lib import call, dtype_code, ptr, stream
+    L = lib.load()
+    nh, H = 12, 768
+    taken = set()
+    for i in (0, 4, 5, 6, 7, 10, 12, 14, 15, 16, 17, 20, 22, 23, 26, 27, 28):
+        row = ATTN_PLAN_ROWS[i]
+        B, Lq, Lk, dtype, impl, wb, p, bits_state, _ = row[:9]
+        assert B == 2
+        plan = attn_plan(L, row, 0, monkeypatch)              # also sets the row's knobs
+        q, k, v, _, bias, _ = _make_attn_inputs(B, Lq, Lk, None, wb, torch.bfloat16 if dtype == "bf16" else torch.float32, seed=i)
+        o, lse = torch.empty_like(q), torch.empty(B, nh, Lq, device=DEV)
+        bits, ready = None, 0
+        if bits_state != "none":
+            bits = torch.zeros(ops._drop_bits_words(B, nh, Lq, Lk), dtype=torch.int64, device=DEV)
+        if bits_state == "ready":
+            call("bevbert_attn_drop_bits", ptr(bits), B, nh, Lq, Lk, p, 11, 0, stream())
+            ready = 1
+        st = ops._strides(q, k, v, o)
+        call("bevbert_attn_fwd", ptr(q), ptr(k), ptr(v), ptr(o), ptr(lse), None, ptr(bias), st, B, nh, Lq, Lk, 64, 0.125,
+             dtype_code(q), impl, p, 11, 0, ptr(bits), ready, stream())
+        do, delta = torch.randn_like(o), torch.empty_like(lse)
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        dbias = torch.zeros(B, nh, Lq, Lk, device=DEV) if wb else None
+        call("bevbert_attn_bwd", ptr(q), ptr(k), ptr(v), ptr(o), ptr(do), ptr(lse), ptr(delta), ptr(dq), ptr(dk), ptr(dv),
+             ptr(dbias), None, ptr(bias), st, B, nh, Lq, Lk, 64, 0.125, dtype_code(q), impl, p, 11, 0, ptr(bits), stream())
+        assert (L.bevbert_attn_last_path(0).decode(), L.bevbert_attn_last_path(1).decode()) == plan, row
+        assert all(bool(torch.isfinite(t.float()).all()) for t in (o, dq, dk, dv)), row
+        taken.update(plan)
+    assert len(taken) == 16, sorted(taken)                    # every kernel of the dispatch ran
+    for name in ("BEVBERT_ATTN_FWD4", "BEVBERT_ATTN_F32", "BEVBERT_ATTN_BWD", "BEVBERT_ATTN_SHORT", "BEVBERT_ATTN_SMALL",
+                 "BEVBERT_ATTN_SMALL_BWD"):
+        monkeypatch.delenv(name, raising=False)
+    B, Lq, Lk, p = 1, 300, 290, 0.1
+    q, k, v, km, _, _ = _make_attn_inputs(B, Lq, Lk, "inf", False, torch.bfloat16, seed=Lq + Lk)
+    do = torch.randn(B, Lq, H, device=DEV, generator=torch.Generator(device=DEV).manual_seed(3)).bfloat16()
+    grads = {}
+    for arm, want in (("0", "attn_bwd2"), (None, "attn_bwd3")):
+        if arm is None:
+            monkeypatch.delenv("BEVBERT_ATTN_BWD3")
+        else:
+            monkeypatch.setenv("BEVBERT_ATTN_BWD3", arm)
+        ops.RT.new_step(4321 + Lk)
+        qi, ki, vi = (t.clone().requires_grad_(True) for t in (q, k, v))
+        ops.RT.trace, ops.RT.paths = {}, {}         # the backward runs on autograd's thread: the call trace reads its path there
+        try:
+            ops._Attention.apply("sep", qi, ki, vi, km, None, nh, p, 2).backward(do)
+            paths = sorted(ops.RT.paths)
+        finally:
+            ops.RT.trace, ops.RT.paths = None, {}
+        assert paths == [f"bevbert_attn_bwd[Lq={Lq},Lk={Lk}] -> {want}", f"bevbert_attn_fwd[Lq={Lq},Lk={Lk}] -> attn_fwd2"]
+        assert L.bevbert_attn_plan(B, nh, Lq, Lk, lib.BF16, 2, 1, 0, p, 1, 1, 0, 0, 1).decode() == want
+        grads[want] = (qi.grad.float(), ki.grad.float(), vi.grad.float())
+    for name, a, b_ in zip(("dq", "dk", "dv"), grads["attn_bwd3"], grads["attn_bwd2"]):
+        scale = max(1.0, float(b_.abs().max()))
+        err = float((a - b_).abs().max())
+        print(f"attn_bwd3 vs attn_bwd2 {name}: max abs diff {err:.3e}, bound {2 ** -7 * scale:.3e}")
+        assert bool(torch.isfinite(a).all()) and err < 2 ** -7 * scale, (name, err, scale)
+
+
 @pytest.mark.parametrize("Lk", [140, 441, 36])
 @pytest.mark.parametrize("impl,dtype", [(1, torch.float32), (2, torch.bfloat16), (3, torch.bfloat16)])
 def test_attention_dropout_matches_exported_mask(ops, impl, dtype, Lk):

@@ -29,7 +29,83 @@ def test_library_builds_loads_and_exports_header_symbols():
                                "bevbert_colsum_workspace_floats", "bevbert_gemm_plan_count", "bevbert_gemm_rejected_count",
                                "bevbert_gemm_plan", "bevbert_colsum_partial_rows", "bevbert_gemm_tuning_export",
                                "bevbert_attn_drop_bits_words", "bevbert_attn_last_path", "bevbert_smallk_workspace_floats",
-                               "bevbert_gemm_tuning_import"} == set(syms)
+                               "bevbert_gemm_tuning_import", "bevbert_attn_plan", "bevbert_attn_bits_ahead"} == set(syms)
+
+
+# The attention dispatch as a table: (B, Lq, Lk, dtype, impl, graph bias, dropout p, keep-bit workspace, knobs) ->
+# (forward kernel, backward kernel).  Workspace: "none" = no pointer, "empty" = passed with bits_ready = 0, "ready" = filled
+# ahead by bevbert_attn_drop_bits.  dbias is wanted wherever there is a bias.  Every row was issued as a real forward +
+# backward call on the commit before attn_plan_fwd / attn_plan_bwd existed (one process per knob arm) and the names are what
+# bevbert_attn_last_path said there; the plan is evaluated for 256 CUs.
+_A = "attn_"
+ATTN_PLAN_ROWS = [
+    (2, 80, 80, "bf16", 2, False, 0.1, "empty", {}, "short_fwd", "short_bwd"),              # text self-attention
+    (2, 96, 96, "bf16", 2, False, 0.1, "empty", {}, "short_fwd", "short_bwd"),
+    (2, 441, 80, "bf16", 2, False, 0.1, "empty", {}, "short_fwd", "mfma_bwd1"),             # BEV <- text
+    (2, 441, 80, "bf16", 2, False, 0.1, "ready", {}, "short_fwd", "mfma_bwd1"),
+    (2, 17, 17, "bf16", 2, True, 0.1, "empty", {}, "mfma_fwd", "mfma_bwd1"),                # global map, graph bias
+    (2, 130, 200, "bf16", 2, True, 0.0, "none", {}, "mfma_fwd", "mfma_bwd"),
+    (2, 100, 140, "bf16", 2, False, 0.1, "empty", {}, "mfma_fwd", "mfma_bwd1"),             # small scores: inline hash
+    (2, 100, 140, "bf16", 2, False, 0.1, "ready", {}, "fwd2", "mfma_bwd1"),
+    (64, 441, 441, "bf16", 2, False, 0.1, "ready", {}, "fwd4", "bwd3"),                     # BEV self-attention: 3 full rounds
+    (32, 441, 441, "bf16", 2, False, 0.1, "ready", {}, "fwd2", "bwd3"),                     # 1.5 rounds
+    (2, 441, 441, "bf16", 2, False, 0.1, "ready", {}, "fwd2", "bwd3"),
+    (2, 441, 441, "bf16", 2, False, 0.1, "none", {}, "mfma_fwd", "mfma_bwd"),               # dropout without a workspace
+    (2, 441, 441, "bf16", 2, False, 0.1, "ready", {"BEVBERT_ATTN_FWD4": "1"}, "fwd4", "bwd3"),
+    (64, 441, 441, "bf16", 2, False, 0.1, "ready", {"BEVBERT_ATTN_FWD4": "0"}, "fwd2", "bwd3"),
+    (2, 80, 441, "bf16", 2, False, 0.0, "none", {}, "fwd2", "bwd3"),                        # MLM: text -> BEV
+    (2, 80, 600, "bf16", 2, False, 0.0, "none", {}, "fwd2", "mfma_bwd"),
+    (2, 80, 80, "bf16", 2, False, 0.1, "empty", {"BEVBERT_ATTN_SHORT": "0"}, "mfma_fwd", "small_bwd2"),
+    (2, 441, 80, "bf16", 2, False, 0.1, "empty", {"BEVBERT_ATTN_SHORT": "0"}, "fwd2", "mfma_bwd1"),
+    (2, 80, 80, "bf16", 2, False, 0.1, "empty", {"BEVBERT_ATTN_SHORT": "0", "BEVBERT_ATTN_SMALL_BWD": "0"}, "mfma_fwd", "mfma_bwd1"),
+    (2, 80, 80, "bf16", 2, False, 0.1, "empty", {"BEVBERT_ATTN_SMALL": "1"}, "small_fwd", "small_bwd2"),
+    (2, 441, 80, "bf16", 2, False, 0.1, "empty", {"BEVBERT_ATTN_SMALL": "1"}, "small_fwd", "small_bwd"),
+    (2, 80, 80, "bf16", 2, False, 0.1, "empty", {"BEVBERT_ATTN_FWD": "1"}, "mfma_fwd", "short_bwd"),
+    (2, 441, 441, "bf16", 2, False, 0.1, "ready", {"BEVBERT_ATTN_BWD3": "0"}, "fwd2", "bwd2"),
+    (2, 441, 441, "bf16", 2, False, 0.1, "ready", {"BEVBERT_ATTN_BWD": "1"}, "fwd2", "mfma_bwd1"),
+    (2, 441, 441, "bf16", 2, False, 0.1, "ready", {"BEVBERT_ATTN_BWD": "split"}, "fwd2", "mfma_bwd"),
+    (2, 441, 441, "bf16", 3, False, 0.1, "ready", {}, "fwd2", "mfma_bwd"),
+    (2, 80, 80, "f32", 0, False, 0.0, "none", {}, "f32_fwd", "f32_bwd"),
+    (2, 80, 80, "f32", 0, False, 0.0, "none", {"BEVBERT_ATTN_F32": "simple"}, "simple_fwd", "simple_bwd"),
+    (2, 80, 80, "bf16", 1, False, 0.0, "none", {}, "simple_fwd", "simple_bwd"),
+]
+ATTN_KNOBS = ("BEVBERT_ATTN_FWD", "BEVBERT_ATTN_BWD", "BEVBERT_ATTN_BWD3", "BEVBERT_ATTN_SMALL", "BEVBERT_ATTN_SMALL_BWD",
+              "BEVBERT_ATTN_SHORT", "BEVBERT_ATTN_FWD4", "BEVBERT_ATTN_F32", "BEVBERT_FWD4_WGS")
+
+
+def attn_plan(l, row, ncu, monkeypatch):
+    """(forward, backward) kernel names bevbert_attn_plan gives a row of ATTN_PLAN_ROWS under the row's knobs."""
+    B, Lq, Lk, dtype, impl, bias, p, bits, env = row[:9]
+    for name in ATTN_KNOBS:
+        monkeypatch.delenv(name, raising=False)
+    for name, value in env.items():
+        monkeypatch.setenv(name, value)
+    code = lib.BF16 if dtype == "bf16" else lib.F32
+    return tuple(l.bevbert_attn_plan(B, 12, Lq, Lk, code, impl, 0, int(bias), p, int(bits != "none"), int(bits == "ready"),
+                                     int(bias), ncu, backward).decode() for backward in (0, 1))
+
+
+def test_attention_dispatch_plan_table(monkeypatch):
+    l = lib.load()
+    for row in ATTN_PLAN_ROWS:
+        assert attn_plan(l, row, 256, monkeypatch) == (_A + row[9], _A + row[10]), row
+    # the occupancy rule of the persistent forward follows the CU count it is handed: 768 items are 2.4 rounds of 320 CUs
+    # (80 % full) and six full rounds of 128
+    bev = ATTN_PLAN_ROWS[8]
+    assert attn_plan(l, bev, 320, monkeypatch)[0] == "attn_fwd2" and attn_plan(l, bev, 128, monkeypatch)[0] == "attn_fwd4"
+    assert l.bevbert_attn_plan(2, 12, 80, 80, lib.F32, 2, 0, 0, 0.0, 0, 0, 0, 256, 0) == b""      # rejected by the calls too
+    # the keep-bit planner's question, against the expression ops_attention.py used to carry
+    lens = (1, 17, 36, 80, 96, 97, 128, 181, 182, 256, 257, 441, 448, 600)
+    for small in (None, "0", "1"):
+        if small is None:
+            monkeypatch.delenv("BEVBERT_ATTN_SMALL", raising=False)
+        else:
+            monkeypatch.setenv("BEVBERT_ATTN_SMALL", small)
+        for Lq in lens:
+            for Lk in lens:
+                for has_bias in (False, True):
+                    old = (Lq * Lk >= 32768 or Lk > 256) and not (Lk <= 96 and not has_bias and small == "1")
+                    assert l.bevbert_attn_bits_ahead(Lq, Lk, int(has_bias)) == int(old), (Lq, Lk, has_bias, small)
 
 
 def test_code_object_targets_gfx950_only():

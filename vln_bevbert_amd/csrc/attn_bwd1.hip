@@ -426,11 +426,7 @@ bool attn_mfma_bwd1_supported(const AttnArgs& a) {
 }
 
 int attn_mfma_bwd1(const AttnArgs& a, hipStream_t st) {
-  BB_REQUIRE(a.ldq % 8 == 0 && a.ldk % 8 == 0 && a.ldv % 8 == 0 && a.ldo % 8 == 0 && a.bsq % 8 == 0 && a.bsk % 8 == 0 &&
-                 a.bsv % 8 == 0 && a.bso % 8 == 0 && ((uintptr_t)a.q % 16) == 0 && ((uintptr_t)a.k % 16) == 0 &&
-                 ((uintptr_t)a.v % 16) == 0 && ((uintptr_t)a.o % 16) == 0 && ((uintptr_t)a.dout % 16) == 0 &&
-                 ((uintptr_t)a.dq % 16) == 0 && ((uintptr_t)a.dk % 16) == 0 && ((uintptr_t)a.dv % 16) == 0,
-             "attention bwd (MFMA path): pointers must be 16-byte aligned and strides multiples of 8 elements");
+  BB_REQUIRE(attn_mfma_operands_aligned(a, true), "attention bwd (MFMA path): " ATTN_MFMA_ALIGN_MSG);
   // BEVBERT_BWD1_WAVES=8: 8 waves x 64 keys (two waves per SIMD, no fragments held in registers) instead of 4 x 112.
   // Measured on the BEV shape (B = 64, 441 x 441, p = 0.1, same box): 303 us vs 262 us -- the re-read fragments cost more
   // LDS time than the second wave hides, so one wave per SIMD is the default.

@@ -419,11 +419,7 @@ bool attn_bwd3_supported(const AttnArgs& a) {
 }
 
 int attn_bwd3(const AttnArgs& a, hipStream_t st) {
-  BB_REQUIRE(a.ldq % 8 == 0 && a.ldk % 8 == 0 && a.ldv % 8 == 0 && a.ldo % 8 == 0 && a.bsq % 8 == 0 && a.bsk % 8 == 0 &&
-                 a.bsv % 8 == 0 && a.bso % 8 == 0 && ((uintptr_t)a.q % 16) == 0 && ((uintptr_t)a.k % 16) == 0 &&
-                 ((uintptr_t)a.v % 16) == 0 && ((uintptr_t)a.o % 16) == 0 && ((uintptr_t)a.dout % 16) == 0 &&
-                 ((uintptr_t)a.dq % 16) == 0 && ((uintptr_t)a.dk % 16) == 0 && ((uintptr_t)a.dv % 16) == 0,
-             "attention bwd (MFMA path): pointers must be 16-byte aligned and strides multiples of 8 elements");
+  BB_REQUIRE(attn_mfma_operands_aligned(a, true), "attention bwd (MFMA path): " ATTN_MFMA_ALIGN_MSG);
   const bool hd = a.drop_p > 0.f, km = a.key_mask != nullptr;
   static const int abl = [] { const char* v = getenv("BEVBERT_B3_ABL"); return v ? atoi(v) : 0; }();
   if (abl && hd && !km) {

@@ -49,6 +49,16 @@ struct AttnArgs {
   int dbg;                 // timing ablations of attn_short.hip (BEVBERT_SHORT_DBG; results WRONG): 1 no output stores, 2 no O loads
 };
 
+// What the bf16 kernels ask of their operands: 16-byte vector loads and stores of rows of 64 bf16 -- every pointer 16-byte
+// aligned, every stride a multiple of 8 elements; the gradients (backward) share the strides of q / k / v / o.
+#define ATTN_MFMA_ALIGN_MSG "pointers must be 16-byte aligned and strides multiples of 8 elements"
+inline bool attn_mfma_operands_aligned(const AttnArgs& a, bool backward) {
+  const auto p16 = [](const void* p) { return (uintptr_t)p % 16 == 0; };
+  return a.ldq % 8 == 0 && a.ldk % 8 == 0 && a.ldv % 8 == 0 && a.ldo % 8 == 0 && a.bsq % 8 == 0 && a.bsk % 8 == 0 &&
+         a.bsv % 8 == 0 && a.bso % 8 == 0 && p16(a.q) && p16(a.k) && p16(a.v) && p16(a.o) &&
+         (!backward || (p16(a.dout) && p16(a.dq) && p16(a.dk) && p16(a.dv)));
+}
+
 // XCD-aware decode of a 1-D grid: hardware places workgroup id on XCD id % 8, each XCD has a private L2.  Work items
 // are numbered (block-in-sequence fastest, then head, then batch) and every XCD takes one contiguous run of them, so
 // the nblk workgroups that share one (batch, head)'s K/V (or Q/dO) tiles hit the same L2.  Bijective for any grid size.

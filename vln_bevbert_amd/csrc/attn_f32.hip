@@ -311,8 +311,7 @@ static bool f32_layout_ok(const AttnArgs& a, bool bwd) {
 }
 // fp32 tensors with 16-byte aligned rows; anything else stays on the wave-per-row kernels
 bool attn_f32_supported(const AttnArgs& a, int dtype, bool bwd) {
-  static const bool off = [] { const char* v = getenv("BEVBERT_ATTN_F32"); return v && v[0] == 's'; }();
-  return !off && dtype == BB_F32 && f32_layout_ok(a, bwd);
+  return dtype == BB_F32 && f32_layout_ok(a, bwd);
 }
 
 int attn_f32_fwd(const AttnArgs& a, hipStream_t st) {

@@ -630,10 +630,7 @@ static int launch_fwd2(const AttnArgs& a_in, hipStream_t st) {
 bool attn_fwd2_supported(const AttnArgs& a) { return a.bias == nullptr && (a.drop_p <= 0.f || a.drop_bits != nullptr); }
 
 int attn_fwd2(const AttnArgs& a, hipStream_t st) {
-  BB_REQUIRE(a.ldq % 8 == 0 && a.ldk % 8 == 0 && a.ldv % 8 == 0 && a.ldo % 8 == 0 && a.bsq % 8 == 0 && a.bsk % 8 == 0 &&
-                 a.bsv % 8 == 0 && a.bso % 8 == 0 && ((uintptr_t)a.q % 16) == 0 && ((uintptr_t)a.k % 16) == 0 &&
-                 ((uintptr_t)a.v % 16) == 0 && ((uintptr_t)a.o % 16) == 0,
-             "attention (MFMA path): pointers must be 16-byte aligned and strides multiples of 8 elements");
+  BB_REQUIRE(attn_mfma_operands_aligned(a, false), "attention (MFMA path): " ATTN_MFMA_ALIGN_MSG);
   // BEVBERT_FWD2_NW in {4, 7}: force a workgroup shape (A/B measurements)
   static const int force = [] { const char* v = getenv("BEVBERT_FWD2_NW"); return v ? atoi(v) : 0; }();
   // 4 waves x 32 queries: four workgroups share a CU (16 waves).  The 7-wave shape (two workgroups of 224 queries cover

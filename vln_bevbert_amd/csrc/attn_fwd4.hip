@@ -378,7 +378,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd4_kernel(AttnArgs a, const uin
 // =============================================================================================
 // launcher
 // =============================================================================================
-static int f4_workgroups() {
+int attn_fwd4_workgroups() {   // also the CU count of the occupancy rule (AttnKnobs, capi.hip)
   static const int ncu = [] {
     int dev = 0, n = 0;
     (void)hipGetDevice(&dev);
@@ -395,7 +395,7 @@ static int launch_fwd4(const AttnArgs& a_in, const uint32_t* bits_l, hipStream_t
                                              hipFuncAttributeMaxDynamicSharedMemorySize, F4Lds::bytes) == hipSuccess;
   BB_REQUIRE(ok, "attention fwd (gen 4): cannot raise the dynamic LDS limit to %d bytes", F4Lds::bytes);
   // one workgroup per CU (its LDS fills the CU), each walking items blockIdx.x, blockIdx.x + gridDim.x, ...
-  const int ncu = f4_workgroups();
+  const int ncu = attn_fwd4_workgroups();
   AttnArgs a = a_in;
   a.nblk = (a.Lq + F4_NQ - 1) / F4_NQ;
   const int nitems = a.nblk * a.nh * a.B;
@@ -428,23 +428,17 @@ static int launch_fwd4(const AttnArgs& a_in, const uint32_t* bits_l, hipStream_t
 // An item fills a CU, so the kernel pays for whole rounds of items: it takes the call when the rounds are at least 85 % full
 // and there are at least two of them (B = 64 x 12 heads = 768 items = 3.0 rounds of 256 CUs: 78.7 against 89.1 us; B = 32:
 // 1.5 rounds, 51.4 against 47.8 us for the 4-wave kernel with its four workgroups per CU; B = 16: 28.6 against 28.0 us).
-// BEVBERT_ATTN_FWD4=1 forces it for every supported shape (tests), =0 switches it off.
-bool attn_fwd4_supported(const AttnArgs& a, const uint32_t* bits_l) {
-  const char* env = getenv("BEVBERT_ATTN_FWD4");      // read per call
-  const int mode = env ? atoi(env) : -1;
-  if (mode == 0) return false;
-  if (!(a.bias == nullptr && a.Lk > 256 && a.Lk <= F4_NK && a.Lq > 256 && (a.drop_p <= 0.f || bits_l != nullptr))) return false;
-  if (mode == 1) return true;
-  const int nitems = (a.Lq + F4_NQ - 1) / F4_NQ * a.nh * a.B, ncu = f4_workgroups();
+// BEVBERT_ATTN_FWD4=1 forces it for every supported shape (tests: `forced`), =0 switches it off (both in capi.hip).
+bool attn_fwd4_supported(const AttnArgs& a, int ncu, bool forced) {
+  if (!(a.bias == nullptr && a.Lk > 256 && a.Lk <= F4_NK && a.Lq > 256 && (a.drop_p <= 0.f || a.drop_bits != nullptr))) return false;
+  if (forced) return true;
+  const int nitems = (a.Lq + F4_NQ - 1) / F4_NQ * a.nh * a.B;
   const int rounds = (nitems + ncu - 1) / ncu;
   return rounds >= 2 && nitems * 100 >= rounds * ncu * 85;
 }
 
 int attn_fwd4(const AttnArgs& a, const uint32_t* bits_l, hipStream_t st) {
-  BB_REQUIRE(a.ldq % 8 == 0 && a.ldk % 8 == 0 && a.ldv % 8 == 0 && a.ldo % 8 == 0 && a.bsq % 8 == 0 && a.bsk % 8 == 0 &&
-                 a.bsv % 8 == 0 && a.bso % 8 == 0 && ((uintptr_t)a.q % 16) == 0 && ((uintptr_t)a.k % 16) == 0 &&
-                 ((uintptr_t)a.v % 16) == 0 && ((uintptr_t)a.o % 16) == 0,
-             "attention (MFMA path): pointers must be 16-byte aligned and strides multiples of 8 elements");
+  BB_REQUIRE(attn_mfma_operands_aligned(a, false), "attention (MFMA path): " ATTN_MFMA_ALIGN_MSG);
   static const int abl = [] { const char* v = getenv("BEVBERT_FWD4_ABL"); return v ? atoi(v) : 0; }();
   if (abl && a.drop_p > 0.f) {
     switch (abl) {

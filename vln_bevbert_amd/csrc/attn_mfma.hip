@@ -555,12 +555,6 @@ __global__ __launch_bounds__(256, KT == 1 ? 2 : 1) void attn_mfma_dkv_kernel(Att
 // =============================================================================================
 // launchers
 // =============================================================================================
-static bool aligned8(const AttnArgs& a) {
-  return a.ldq % 8 == 0 && a.ldk % 8 == 0 && a.ldv % 8 == 0 && a.ldo % 8 == 0 && a.bsq % 8 == 0 && a.bsk % 8 == 0 &&
-         a.bsv % 8 == 0 && a.bso % 8 == 0 && ((uintptr_t)a.q % 16) == 0 && ((uintptr_t)a.k % 16) == 0 &&
-         ((uintptr_t)a.v % 16) == 0 && ((uintptr_t)a.o % 16) == 0;
-}
-
 // Tile-shape knobs for A/B measurements (read once): BEVBERT_FWD_QT / BEVBERT_DQ_QT / BEVBERT_DKV_KT in {1, 2}.
 static int env_knob(const char* name, int dflt) {
   const char* v = getenv(name);
@@ -583,7 +577,7 @@ static int env_knob(const char* name, int dflt) {
 int attn_mfma_fwd(const AttnArgs& a_in, hipStream_t st) {
   const AttnArgs& a = a_in;
   static const int fwd_qt = env_knob("BEVBERT_FWD_QT", 2);
-  BB_REQUIRE(aligned8(a), "attention (MFMA path): pointers must be 16-byte aligned and strides multiples of 8 elements");
+  BB_REQUIRE(attn_mfma_operands_aligned(a, false), "attention (MFMA path): " ATTN_MFMA_ALIGN_MSG);
   if (a.Lq > 64 && fwd_qt == 2)
     BB_DISPATCH_FLAGS(attn_mfma_fwd_kernel, 2, (a.Lq + 127) / 128, 0);
   else
@@ -600,7 +594,7 @@ static bool raise_lds_limit() {
 
 int attn_mfma_bwd(const AttnArgs& a_in, hipStream_t st) {
   const AttnArgs& a = a_in;
-  BB_REQUIRE(aligned8(a), "attention (MFMA path): pointers must be 16-byte aligned and strides multiples of 8 elements");
+  BB_REQUIRE(attn_mfma_operands_aligned(a, false), "attention (MFMA path): " ATTN_MFMA_ALIGN_MSG);
   BB_REQUIRE(((uintptr_t)a.dout % 16) == 0 && ((uintptr_t)a.dq % 16) == 0 && ((uintptr_t)a.dk % 16) == 0 &&
                  ((uintptr_t)a.dv % 16) == 0, "attention bwd (MFMA path): gradient pointers must be 16-byte aligned");
   static const int dq_qt = env_knob("BEVBERT_DQ_QT", 2), dkv_kt = env_knob("BEVBERT_DKV_KT", 1);

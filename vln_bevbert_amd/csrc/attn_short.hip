@@ -433,25 +433,12 @@ __global__ __launch_bounds__(384) void attn_short_bwd_kernel(AttnArgs a) {
 // =============================================================================================
 #define SH_MAX_LEN 96
 
-static bool sh_aligned(const AttnArgs& a) {
-  return a.ldq % 8 == 0 && a.ldk % 8 == 0 && a.ldv % 8 == 0 && a.ldo % 8 == 0 && a.bsq % 8 == 0 && a.bsk % 8 == 0 &&
-         a.bsv % 8 == 0 && a.bso % 8 == 0 && ((uintptr_t)a.q % 16) == 0 && ((uintptr_t)a.k % 16) == 0 &&
-         ((uintptr_t)a.v % 16) == 0 && ((uintptr_t)a.o % 16) == 0;
-}
-
 static int sh_round_tiles(int n) {     // tile counts the kernels are instantiated for
   return n <= 2 ? 2 : n <= 3 ? 3 : n <= 5 ? 5 : 6;
 }
 
-// BEVBERT_ATTN_SHORT=0 (read per call): the kernels of rounds 2-5 (A/B measurements, the on-GPU cross-check)
-static bool sh_on() {
-  const char* v = getenv("BEVBERT_ATTN_SHORT");
-  return !(v && v[0] == '0');
-}
-
 bool attn_short_fwd_supported(const AttnArgs& a, bool bits_ready) {
-  if (!sh_on()) return false;
-  return a.bias == nullptr && a.Lk <= SH_MAX_LEN && sh_aligned(a) &&
+  return a.bias == nullptr && a.Lk <= SH_MAX_LEN && attn_mfma_operands_aligned(a, false) &&
          !(a.drop_p > 0.f && bits_ready && a.drop_bits == nullptr);
 }
 
@@ -485,10 +472,8 @@ int attn_short_fwd(const AttnArgs& a_in, bool bits_ready, hipStream_t st) {
 }
 
 bool attn_short_bwd_supported(const AttnArgs& a) {
-  if (!sh_on()) return false;
-  return a.bias == nullptr && a.dbias == nullptr && a.Lk <= SH_MAX_LEN && a.Lq <= SH_MAX_LEN && sh_aligned(a) &&
-         (a.drop_p <= 0.f || a.drop_bits != nullptr) && ((uintptr_t)a.dout % 16) == 0 && ((uintptr_t)a.dq % 16) == 0 &&
-         ((uintptr_t)a.dk % 16) == 0 && ((uintptr_t)a.dv % 16) == 0;
+  return a.bias == nullptr && a.dbias == nullptr && a.Lk <= SH_MAX_LEN && a.Lq <= SH_MAX_LEN &&
+         attn_mfma_operands_aligned(a, true) && (a.drop_p <= 0.f || a.drop_bits != nullptr);
 }
 
 template <int NKT, int NQT>

@@ -565,18 +565,13 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(5))) void a
 // =============================================================================================
 // Host side
 // =============================================================================================
-static bool sm_aligned(const AttnArgs& a) {
-  return a.ldq % 8 == 0 && a.ldk % 8 == 0 && a.ldv % 8 == 0 && a.ldo % 8 == 0 && a.bsq % 8 == 0 && a.bsk % 8 == 0 &&
-         a.bsv % 8 == 0 && a.bso % 8 == 0 && ((uintptr_t)a.q % 16) == 0 && ((uintptr_t)a.k % 16) == 0 &&
-         ((uintptr_t)a.v % 16) == 0 && ((uintptr_t)a.o % 16) == 0;
+bool attn_small_fwd_supported(const AttnArgs& a) {
+  return a.bias == nullptr && a.Lk <= 16 * SM_MAXKT && attn_mfma_operands_aligned(a, false);
 }
 
-bool attn_small_fwd_supported(const AttnArgs& a) { return a.bias == nullptr && a.Lk <= 16 * SM_MAXKT && sm_aligned(a); }
-
 bool attn_small_bwd_supported(const AttnArgs& a) {
-  return a.bias == nullptr && a.dbias == nullptr && a.Lk <= 16 * SM_MAXKT && sm_aligned(a) &&
-         (a.drop_p <= 0.f || a.drop_bits != nullptr) && ((uintptr_t)a.dout % 16) == 0 && ((uintptr_t)a.dq % 16) == 0 &&
-         ((uintptr_t)a.dk % 16) == 0 && ((uintptr_t)a.dv % 16) == 0;
+  return a.bias == nullptr && a.dbias == nullptr && a.Lk <= 16 * SM_MAXKT && attn_mfma_operands_aligned(a, true) &&
+         (a.drop_p <= 0.f || a.drop_bits != nullptr);
 }
 
 template <int NKT>

@@ -164,6 +164,10 @@ def load():
     lib.bevbert_version.restype = _I
     lib.bevbert_attn_last_path.restype = ctypes.c_char_p
     lib.bevbert_attn_last_path.argtypes = [_I]
+    lib.bevbert_attn_plan.restype = ctypes.c_char_p
+    lib.bevbert_attn_plan.argtypes = [_I] * 8 + [_F] + [_I] * 5
+    lib.bevbert_attn_bits_ahead.restype = _I
+    lib.bevbert_attn_bits_ahead.argtypes = [_I, _I, _I]
     lib.bevbert_hip_error_reset.restype = _I
     lib.bevbert_colsum_workspace_floats.restype = _I64
     lib.bevbert_colsum_workspace_floats.argtypes = [_I]

@@ -1,11 +1,10 @@
 """Attention entry points (ops.py re-exports everything here): one autograd Function over bevbert_attn_fwd / _bwd for
 self-, cross- and graph-biased attention, with the keep-bit workspace of the dropout mask."""
 import math
-import os as _os
 
 import torch
 
-from .lib import dtype_code, ptr, stream
+from .lib import dtype_code, load, ptr, stream
 from .ops_core import ATTN_BITS, HEAD_DIM, RT, _drop_bits_words, _mark_touched, _sink, call
 
 
@@ -17,6 +16,10 @@ def _strides(q, k, v, o):
     arr = (ctypes.c_int64 * 8)(q.stride(1), k.stride(1), v.stride(1), o.stride(1),
                                q.stride(0), k.stride(0), v.stride(0), o.stride(0))
     return arr
+
+
+def _bits_ahead(Lq, Lk, has_bias):
+    return load().bevbert_attn_bits_ahead(Lq, Lk, int(has_bias))
 
 
 class _Attention(torch.autograd.Function):
@@ -49,11 +52,9 @@ class _Attention(torch.autograd.Function):
             # keep-bit workspace of the dropout mask (1 bit / element in the forward's and in the backward's lane
             # layout: 2 x 19 MB at 64x12x441x441), filled by the library ahead of the forward kernel; both directions
             # read bits through the scalar cache instead of hashing per element
-            # attn_small.hip (opt-in, BEVBERT_ATTN_SMALL=1) hashes inline whatever the query count
-            short_keys = Lk <= 96 and bias is None and _os.environ.get("BEVBERT_ATTN_SMALL") == "1"
-            if (Lq * Lk >= 32768 or Lk > 256) and not short_keys:
+            if _bits_ahead(Lq, Lk, bias is not None):
                 bits, bits_ready = ATTN_BITS.get(B, nh, Lq, Lk, drop_p, off, q.device)
-            else:       # small score matrices: the forward hashes inline and leaves the bits for the backward (capi.hip)
+            else:       # the forward hashes inline and leaves the bits for the backward (attn_bits_ahead, capi.hip)
                 bits = torch.empty(_drop_bits_words(B, nh, Lq, Lk), dtype=torch.int64, device=q.device)
         call("bevbert_attn_fwd", ptr(q), ptr(k), ptr(v), ptr(o), ptr(lse), ptr(key_mask), ptr(bias),
              _strides(q, k, v, o), B, nh, Lq, Lk, HEAD_DIM, scale, dtype_code(q), impl, float(drop_p), RT.seed, off,
