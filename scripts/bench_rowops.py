@@ -145,7 +145,7 @@ def extra():
     dy = torch.randn(rows, H, device=dev).bfloat16()
     z, dz, add = torch.randn_like(dy), torch.empty_like(dy), torch.randn_like(dy)
     mean, rstd, gamma = torch.zeros(rows, device=dev), torch.ones(rows, device=dev), torch.ones(H, device=dev)
-    ws = torch.empty(512 * 3 * 3072, device=dev)
+    ws = torch.empty(int(__import__("vln_bevbert_amd.lib", fromlist=["load"]).load().bevbert_colsum_workspace_floats(3 * H)), device=dev)
     t = timeit(lambda: call("bevbert_layernorm_bwd_add", ptr(dy), ptr(z), ptr(mean), ptr(rstd), ptr(gamma), ptr(dz), None, ptr(add),
                             None, None, None, ptr(ws), rows, H, BF16, 0.0, 1, 0, 0, stream()))
     print(json.dumps({"kernel": "ln_bwd_add", "rows": rows, "us": round(t, 2), "bytes": rows * H * 2 * 4, "mark": _mark_idx[0], "GBps": round(rows * H * 8 / t / 1e3, 1)}), flush=True)

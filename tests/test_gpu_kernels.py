@@ -141,11 +141,8 @@ def _ln_ref(x, bias, res, g, b, eps, keep=None, p=0.0):
     return torch.nn.functional.layer_norm(z, (z.shape[-1],), g, b, eps), z
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("with_res,p", [(True, 0.0), (True, 0.1), (False, 0.0), (False, 0.3)])
-def test_layernorm_fwd_bwd(ops, dtype, with_res, p):
+def _check_layernorm_fwd_bwd(ops, dtype, with_res, p, rows, H):
     torch.manual_seed(0)
-    rows, H = 517, 768
     x = torch.randn(rows, H, device=DEV).to(dtype)
     res = torch.randn(rows, H, device=DEV).to(dtype) if with_res else None
     bias = (0.1 * torch.randn(H, device=DEV)).requires_grad_(True)
@@ -158,7 +155,7 @@ def test_layernorm_fwd_bwd(ops, dtype, with_res, p):
     rin = res.clone().requires_grad_(True) if with_res else None
     y = ops.bias_dropout_residual_layernorm(xin, bias, rin, gam, bet, 1e-12, p, training=True, inplace_z=False)
     keep = ops.dropout_keep_mask(rows * H, p, ops.RT.seed, 0, DEV).view(rows, H) if p > 0 else None
-    if keep is not None:
+    if keep is not None and keep.numel() >= 1 << 16:      # 0.01 is over 5 sigma of the keep rate from 65 536 elements up
         assert abs(float(keep.float().mean()) - (1 - p)) < 0.01
     bias_r, gam_r, bet_r = (t.detach().clone().requires_grad_(True) for t in (bias, gam, bet))
     yr, _ = _ln_ref(xr, bias_r, rr, gam_r, bet_r, 1e-12, keep, p)
@@ -177,15 +174,45 @@ def test_layernorm_fwd_bwd(ops, dtype, with_res, p):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("p", [0.0, 0.2])
-def test_prenorm_residual_layernorm_returns_the_stream_and_folds_its_gradient(ops, dtype, p):
+@pytest.mark.parametrize("with_res,p", [(True, 0.0), (True, 0.1), (False, 0.0), (False, 0.3)])
+def test_layernorm_fwd_bwd(ops, dtype, with_res, p):
+    _check_layernorm_fwd_bwd(ops, dtype, with_res, p, 517, 768)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("rows", [1, 7])
+@pytest.mark.parametrize("H", [256, 512, 1024])
+def test_layernorm_every_width(ops, dtype, rows, H):
+    """The plain forward / backward at the widths next to 768, with bias, residual and p = 0.1.  Seven rows: one full
+    group of four and a partial one in the forward; in the backward one workgroup in which a wave takes two rows, a wave
+    takes one, and the grid-stride loop ends unevenly."""
+    _check_layernorm_fwd_bwd(ops, dtype, True, 0.1, rows, H)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("H", [1536, 2048])
+def test_layernorm_every_width_forward_only(ops, dtype, H):
+    """The two widths only the plain forward is instantiated for, same composition, no autograd."""
+    torch.manual_seed(0)
+    rows, p = 7, 0.1
+    x, res = (torch.randn(rows, H, device=DEV).to(dtype) for _ in range(2))
+    bias, bet = (0.1 * torch.randn(H, device=DEV) for _ in range(2))
+    gam = 1 + 0.1 * torch.randn(H, device=DEV)
+    ops.RT.new_step(1234)
+    with torch.no_grad():
+        y = ops.bias_dropout_residual_layernorm(x, bias, res, gam, bet, 1e-12, p, training=True, inplace_z=False)
+        keep = ops.dropout_keep_mask(rows * H, p, ops.RT.seed, 0, DEV).view(rows, H)
+        yr, _ = _ln_ref(x, bias, res, gam, bet, 1e-12, keep, p)
+    assert float((y.float() - yr).abs().max()) < (1e-4 if dtype == torch.float32 else 2e-2)
+
+
+def _check_prenorm(ops, dtype, p, rows, H):
     """ops.bias_dropout_residual_prenorm: (LayerNorm(z), z) with z = residual + dropout(x + bias) -- the residual add of a
     pre-norm block and the LayerNorm opening the next sub-layer in one launch (transformer.py:170-182); BOTH outputs are
     used downstream, and the gradient arriving at z is added to LayerNorm's input gradient inside the backward kernel
     (bevbert_layernorm_bwd_add).  Against the torch composition with the exported keep mask; the no-grad call gives the
     same two tensors."""
     torch.manual_seed(1)
-    rows, H = 389, 768
     x = torch.randn(rows, H, device=DEV).to(dtype)
     res = torch.randn(rows, H, device=DEV).to(dtype)
     bias = (0.1 * torch.randn(H, device=DEV)).requires_grad_(True)
@@ -216,6 +243,18 @@ def test_prenorm_residual_layernorm_returns_the_stream_and_folds_its_gradient(op
     _, z3 = ops.bias_dropout_residual_prenorm(xin2, bias, rin2, gam, bet, 1e-5, p, training=True)
     (z3.float() * dz).sum().backward()
     assert rel_err(rin2.grad, dz.to(dtype)) < 1e-6 if dtype == torch.float32 else rel_err(rin2.grad, dz) < 1e-2
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("p", [0.0, 0.2])
+def test_prenorm_residual_layernorm_returns_the_stream_and_folds_its_gradient(ops, dtype, p):
+    _check_prenorm(ops, dtype, p, 389, 768)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("p", [0.0, 0.2])
+def test_layernorm_every_width_prenorm(ops, dtype, p):
+    _check_prenorm(ops, dtype, p, 7, 256)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -437,9 +476,8 @@ def test_semantic_head_loss_select_and_bce(ops, dtype):
     assert torch.equal(idx2, torch.arange(100, device=DEV)) and float(valid2.sum()) == 100 and float(denom2) == N * C
 
 
-def test_embed_sum_layernorm(ops):
+def _check_embed_sum_layernorm(ops, V, H, B, L):
     torch.manual_seed(3)
-    V, H, B, L = 500, 768, 3, 17
     word = torch.randn(V, H, device=DEV, requires_grad=True)
     pos = torch.randn(64, H, device=DEV, requires_grad=True)
     typ = torch.randn(2, H, device=DEV, requires_grad=True)
@@ -457,6 +495,14 @@ def test_embed_sum_layernorm(ops):
     yr.backward(dy)
     for a_, r_ in zip((word, pos, typ, g, b), ref_in):
         assert rel_err(a_.grad, r_.grad) < 1e-4
+
+
+def test_embed_sum_layernorm(ops):
+    _check_embed_sum_layernorm(ops, 500, 768, 3, 17)
+
+
+def test_layernorm_every_width_gather(ops):
+    _check_embed_sum_layernorm(ops, 11, 512, 2, 5)
 
 
 @pytest.mark.parametrize("table_rows,rows,dtype", [(2, 28224, torch.bfloat16), (3, 11520, torch.bfloat16),

@@ -142,6 +142,32 @@ def test_invalid_arguments_are_rejected_without_a_gpu():
         assert rc == -1 and b"must be 256, 512, 768 or 1024" in l.bevbert_last_error(), (H, rc)
 
 
+def test_layernorm_width_and_dtype_dispatch_answers_without_a_gpu():
+    """What the plain LayerNorm entries answer for a width or dtype they have no kernel for (rows = 1, null pointers: the
+    answer comes before any launch).  The forward is instantiated for H / 256 in {1, 2, 3, 4, 6, 8}, the backward for 1..4."""
+    l = lib.load()
+    N = None
+    entries = {
+        "fwd": lambda H, dt: l.bevbert_bias_dropout_residual_layernorm_fwd(N, N, N, N, N, N, N, N, N, 1, H, 1e-12, dt, 0.0, 0, 0, N),
+        "post_fwd": lambda H, dt: l.bevbert_layernorm_post_fwd(N, N, N, N, N, N, N, N, N, N, 1, H, 1e-12, dt, N),
+        "embed_fwd": lambda H, dt: l.bevbert_embed_sum_layernorm_fwd(N, N, N, N, N, N, N, N, N, N, 1, 1, H, 1e-12, dt, 0.0, 0, 0, N),
+        "bwd": lambda H, dt: l.bevbert_layernorm_bwd(N, N, N, N, N, N, N, N, N, N, N, 1, H, dt, 0.0, 0, 0, 0, N),
+        "bwd_add": lambda H, dt: l.bevbert_layernorm_bwd_add(N, N, N, N, N, N, N, N, N, N, N, N, 1, H, dt, 0.0, 0, 0, 0, N),
+    }
+    for name, f in entries.items():
+        bwd = name.startswith("bwd")
+        for dt in (0, 1):
+            rc = f(1536 if bwd else 1280, dt)
+            want = b"layernorm_bwd: H=1536 unsupported" if bwd else b"H=1280 unsupported"
+            assert rc == -3 and want in l.bevbert_last_error(), (name, dt, rc, l.bevbert_last_error())
+            rc = f(100, dt)
+            want = b"bad shape rows=1 L=1 H=100" if name == "embed_fwd" else b"multiple of 256"
+            assert rc == -1 and want in l.bevbert_last_error(), (name, dt, rc, l.bevbert_last_error())
+        for H in (768, 1280, 1536):       # the dtype is looked at before the width
+            rc = f(H, 2)
+            assert rc == -3 and b"dtype 2 unsupported" in l.bevbert_last_error(), (name, H, rc, l.bevbert_last_error())
+
+
 def test_cpu_tensors_fail_loudly():
     from vln_bevbert_amd import ops
     with pytest.raises(lib.BevBertHipError):

@@ -12,6 +12,7 @@
 // Layout: activations are (rows, H) row-major with H % 256 == 0; one 64-lane wave owns one row and keeps it in
 // registers (H/64 values per lane as float4s), so each tensor is read once and written once; statistics are fp32.
 #include <math.h>
+#include <type_traits>
 
 #include "common.h"
 
@@ -510,27 +511,26 @@ __global__ __launch_bounds__(256) void colwise_bwd_kernel(const T* __restrict__ 
   if (MODE != 1) b = *reinterpret_cast<const float4*>(bias + c0);
   // block b owns the CONTIGUOUS rows [b * rpb, (b + 1) * rpb): the eight rows a thread has in flight are neighbours
   const int rpb = (rows + (int)gridDim.x - 1) / (int)gridDim.x;
-  const int stride = 1;
   int r = blockIdx.x * rpb;
   rows = (r + rpb < rows) ? r + rpb : rows;
   constexpr int R = 8;                   // rows in flight per thread
-  for (; r + (R - 1) * stride < rows; r += R * stride) {
+  for (; r + R - 1 < rows; r += R) {
     float4 d[R], a[R];
 #pragma unroll
     for (int k = 0; k < R; ++k) {
-      d[k] = ld4<T>(dy + (size_t)(r + k * stride) * C + c0);
-      if (MODE != 1) a[k] = ld4<T>(x + (size_t)(r + k * stride) * C + c0);
+      d[k] = ld4<T>(dy + (size_t)(r + k) * C + c0);
+      if (MODE != 1) a[k] = ld4<T>(x + (size_t)(r + k) * C + c0);
     }
 #pragma unroll
     for (int k = 0; k < R; ++k) {
       if (MODE != 1) {
         d[k] = act_grad4_of<T, MODE == 2 ? 1 : 0>(d[k], a[k], b);
-        st4<T>(dx + (size_t)(r + k * stride) * C + c0, d[k]);
+        st4<T>(dx + (size_t)(r + k) * C + c0, d[k]);
       }
       acc.x += d[k].x; acc.y += d[k].y; acc.z += d[k].z; acc.w += d[k].w;
     }
   }
-  for (; r < rows; r += stride) {
+  for (; r < rows; ++r) {
     float4 d = ld4<T>(dy + (size_t)r * C + c0);
     if (MODE != 1) {
       const float4 a = ld4<T>(x + (size_t)r * C + c0);
@@ -1104,25 +1104,46 @@ BEVBERT_API int bevbert_graph_bias_bwd(const float* dbias, const float* dists, i
 // =============================================================================================
 // C ABI
 // =============================================================================================
-template <typename T, bool GATHER>
-static int ln_fwd_dispatch(int NV, dim3 grid, hipStream_t st, const void* x, const float* bias, const void* residual,
-                           const float* gamma, const float* beta, void* y, void* z_out, float* mean, float* rstd,
-                           int rows, float eps, float p, uint64_t seed, uint64_t offset, const int64_t* ids,
-                           const void* word, const void* pos, const void* type_row, int L) {
+// Compile-time selection for the LayerNorm entries: f(T{}) with the activation type of `dtype`, f(integral_constant<NV>)
+// with NV = H / 256 when it is one of Ns...; false when there is no such type / width (f is not called).
+template <typename F>
+static bool with_act_type(int dtype, F&& f) {
+  if (dtype == BB_F32) f(float{});
+  else if (dtype == BB_BF16) f(bf16_raw{});
+  else return false;
+  return true;
+}
+template <int... Ns, typename F>
+static bool with_width(int H, F&& f) {
+  return ((H / 256 == Ns ? (f(std::integral_constant<int, Ns>{}), true) : false) || ...);
+}
+
+// the three plain forward entries behind their argument checks; `name` as in their messages
+template <bool GATHER>
+static int ln_fwd_launch(const char* name, hipStream_t st, const void* x, const float* bias, const void* residual,
+                         const float* gamma, const float* beta, void* y, void* z_out, float* mean, float* rstd,
+                         int rows, int H, float eps, int dtype, float p, uint64_t seed, uint64_t offset,
+                         const int64_t* ids, const void* word, const void* pos, const void* type_row, int L) {
+  const dim3 grid((rows + 3) / 4);
   const uint32_t thr = bb_drop_threshold(p);
-#define GO(N)                                                                                                        \
-  case N:                                                                                                            \
-    hipLaunchKernelGGL((ln_fwd_kernel<T, N, GATHER>), grid, dim3(256), 0, st, (const T*)x, bias, (const T*)residual, \
-                       gamma, beta, (T*)y, (T*)z_out, mean, rstd, rows, eps, p, thr, bb_site_key(seed, offset), ids, \
-                       (const T*)word, (const T*)pos, (const T*)type_row, L, bb_step_salt());                        \
-    break;
-  switch (NV) {
-    GO(1) GO(2) GO(3) GO(4) GO(6) GO(8)
-    default:
-      bb_set_error("layernorm: H=%d unsupported (need H in {256,512,768,1024,1536,2048})", NV * 256);
-      return BB_EUNSUPPORTED;
+  bool width_ok = false;
+  const bool type_ok = with_act_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    width_ok = with_width<1, 2, 3, 4, 6, 8>(H, [&](auto nv) {
+      hipLaunchKernelGGL((ln_fwd_kernel<T, decltype(nv)::value, GATHER>), grid, dim3(256), 0, st, (const T*)x, bias, (const T*)residual,
+                         gamma, beta, (T*)y, (T*)z_out, mean, rstd, rows, eps, p, thr, bb_site_key(seed, offset), ids,
+                         (const T*)word, (const T*)pos, (const T*)type_row, L, bb_step_salt());
+    });
+  });
+  if (!type_ok) {
+    bb_set_error("%s: dtype %d unsupported", name, dtype);
+    return BB_EUNSUPPORTED;
   }
-#undef GO
+  if (!width_ok) {
+    bb_set_error("layernorm: H=%d unsupported (need H in {256,512,768,1024,1536,2048})", H);
+    return BB_EUNSUPPORTED;
+  }
+  BB_CHECK_LAUNCH(name);
   return BB_OK;
 }
 
@@ -1134,21 +1155,8 @@ BEVBERT_API int bevbert_bias_dropout_residual_layernorm_fwd(const void* x, const
   BB_REQUIRE(rows >= 0 && H % 256 == 0, "layernorm_fwd: H=%d must be a multiple of 256", H);
   BB_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "layernorm_fwd: dropout p=%f", drop_p);
   if (rows == 0) return BB_OK;
-  const dim3 grid((rows + 3) / 4);
-  int rc;
-  if (dtype == BB_F32)
-    rc = ln_fwd_dispatch<float, false>(H / 256, grid, stream, x, bias, residual, gamma, beta, y, z_out, mean, rstd,
-                                       rows, eps, drop_p, seed, offset, nullptr, nullptr, nullptr, nullptr, 1);
-  else if (dtype == BB_BF16)
-    rc = ln_fwd_dispatch<bf16_raw, false>(H / 256, grid, stream, x, bias, residual, gamma, beta, y, z_out, mean, rstd,
-                                          rows, eps, drop_p, seed, offset, nullptr, nullptr, nullptr, nullptr, 1);
-  else {
-    bb_set_error("layernorm_fwd: dtype %d unsupported", dtype);
-    return BB_EUNSUPPORTED;
-  }
-  if (rc != BB_OK) return rc;
-  BB_CHECK_LAUNCH("layernorm_fwd");
-  return BB_OK;
+  return ln_fwd_launch<false>("layernorm_fwd", stream, x, bias, residual, gamma, beta, y, z_out, mean, rstd, rows, H, eps,
+                              dtype, drop_p, seed, offset, nullptr, nullptr, nullptr, nullptr, 1);
 }
 
 // y = LayerNorm(x + bias) + post1 + post2 (either may be NULL): the element-wise sums that follow a LayerNorm in the
@@ -1158,21 +1166,8 @@ BEVBERT_API int bevbert_layernorm_post_fwd(const void* x, const float* bias, con
                                            float* rstd, int rows, int H, float eps, int dtype, hipStream_t stream) {
   BB_REQUIRE(rows >= 0 && H % 256 == 0, "layernorm_post_fwd: H=%d must be a multiple of 256", H);
   if (rows == 0) return BB_OK;
-  const dim3 grid((rows + 3) / 4);
-  int rc;
-  if (dtype == BB_F32)
-    rc = ln_fwd_dispatch<float, false>(H / 256, grid, stream, x, bias, nullptr, gamma, beta, y, z_out, mean, rstd, rows,
-                                       eps, 0.f, 0, 0, nullptr, post1, post2, nullptr, 1);
-  else if (dtype == BB_BF16)
-    rc = ln_fwd_dispatch<bf16_raw, false>(H / 256, grid, stream, x, bias, nullptr, gamma, beta, y, z_out, mean, rstd,
-                                          rows, eps, 0.f, 0, 0, nullptr, post1, post2, nullptr, 1);
-  else {
-    bb_set_error("layernorm_post_fwd: dtype %d unsupported", dtype);
-    return BB_EUNSUPPORTED;
-  }
-  if (rc != BB_OK) return rc;
-  BB_CHECK_LAUNCH("layernorm_post_fwd");
-  return BB_OK;
+  return ln_fwd_launch<false>("layernorm_post_fwd", stream, x, bias, nullptr, gamma, beta, y, z_out, mean, rstd, rows, H,
+                              eps, dtype, 0.f, 0, 0, nullptr, post1, post2, nullptr, 1);
 }
 
 BEVBERT_API int bevbert_embed_sum_layernorm_fwd(const int64_t* ids, const void* word, const void* pos,
@@ -1182,21 +1177,8 @@ BEVBERT_API int bevbert_embed_sum_layernorm_fwd(const int64_t* ids, const void* 
                                                 hipStream_t stream) {
   BB_REQUIRE(rows >= 0 && H % 256 == 0 && L > 0, "embed_sum_layernorm_fwd: bad shape rows=%d L=%d H=%d", rows, L, H);
   if (rows == 0) return BB_OK;
-  const dim3 grid((rows + 3) / 4);
-  int rc;
-  if (dtype == BB_F32)
-    rc = ln_fwd_dispatch<float, true>(H / 256, grid, stream, nullptr, nullptr, nullptr, gamma, beta, y, z_out, mean,
-                                      rstd, rows, eps, drop_p, seed, offset, ids, word, pos, type_row, L);
-  else if (dtype == BB_BF16)
-    rc = ln_fwd_dispatch<bf16_raw, true>(H / 256, grid, stream, nullptr, nullptr, nullptr, gamma, beta, y, z_out, mean,
-                                         rstd, rows, eps, drop_p, seed, offset, ids, word, pos, type_row, L);
-  else {
-    bb_set_error("embed_sum_layernorm_fwd: dtype %d unsupported", dtype);
-    return BB_EUNSUPPORTED;
-  }
-  if (rc != BB_OK) return rc;
-  BB_CHECK_LAUNCH("embed_sum_layernorm_fwd");
-  return BB_OK;
+  return ln_fwd_launch<true>("embed_sum_layernorm_fwd", stream, nullptr, nullptr, nullptr, gamma, beta, y, z_out, mean,
+                             rstd, rows, H, eps, dtype, drop_p, seed, offset, ids, word, pos, type_row, L);
 }
 
 // row groups of the column kernels (and of the LayerNorm backward, whose partial rows go through the same second stage):
@@ -1219,7 +1201,6 @@ static int colwise_blocks(int rows) {
   if (nb > colwise_max_blocks()) nb = colwise_max_blocks();
   return nb < 1 ? 1 : nb;
 }
-static int partial_blocks(int rows, int) { return colwise_blocks(rows); }
 
 // row groups of a purely elementwise row kernel (no partial rows to bound): 8 rows each, at most 4096 groups
 static int elementwise_row_groups(int rows) {
@@ -1247,7 +1228,33 @@ BEVBERT_API int bevbert_colsum_finalize(const float* partials, int nblocks, int 
 static int layernorm_bwd_impl(const void* dy, const void* z, const float* mean, const float* rstd, const float* gamma,
                               void* dz, void* dx, const void* dz_add, float* dgamma, float* dbeta, float* dbias,
                               float* workspace, int rows, int H, int dtype, float drop_p, uint64_t seed, uint64_t offset,
-                              int accumulate, hipStream_t stream);
+                              int accumulate, hipStream_t stream) {
+  BB_REQUIRE(H % 256 == 0, "layernorm_bwd: H=%d must be a multiple of 256", H);
+  if (rows <= 0) return BB_OK;
+  const int nb = colwise_blocks(rows);
+  const uint32_t thr = bb_drop_threshold(drop_p);
+  bool width_ok = false;
+  const bool type_ok = with_act_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    width_ok = with_width<1, 2, 3, 4>(H, [&](auto nv) {
+      hipLaunchKernelGGL((ln_bwd_kernel<T, decltype(nv)::value>), dim3(nb), dim3(256), 0, stream, (const T*)dy, (const T*)z, mean, rstd,
+                         gamma, (T*)dz, (T*)dx, workspace, rows, drop_p, thr, bb_site_key(seed, offset), bb_step_salt(),
+                         (const T*)dz_add);
+    });
+  });
+  if (!type_ok) {
+    bb_set_error("layernorm_bwd: dtype %d unsupported", dtype);
+    return BB_EUNSUPPORTED;
+  }
+  if (!width_ok) {
+    bb_set_error("layernorm_bwd: H=%d unsupported", H);
+    return BB_EUNSUPPORTED;
+  }
+  BB_CHECK_LAUNCH("layernorm_bwd");
+  if (dgamma || dbeta || dbias) launch_finalize(workspace, nb, 3, H, dgamma, dbeta, dbias, accumulate, stream);
+  BB_CHECK_LAUNCH("layernorm_bwd finalize");
+  return BB_OK;
+}
 
 BEVBERT_API int bevbert_layernorm_bwd(const void* dy, const void* z, const float* mean, const float* rstd,
                                       const float* gamma, void* dz, void* dx, float* dgamma, float* dbeta,
@@ -1269,38 +1276,6 @@ BEVBERT_API int bevbert_layernorm_bwd_add(const void* dy, const void* z, const f
                             drop_p, seed, offset, accumulate, stream);
 }
 
-static int layernorm_bwd_impl(const void* dy, const void* z, const float* mean, const float* rstd, const float* gamma,
-                              void* dz, void* dx, const void* dz_add, float* dgamma, float* dbeta, float* dbias,
-                              float* workspace, int rows, int H, int dtype, float drop_p, uint64_t seed, uint64_t offset,
-                              int accumulate, hipStream_t stream) {
-  BB_REQUIRE(H % 256 == 0, "layernorm_bwd: H=%d must be a multiple of 256", H);
-  if (rows <= 0) return BB_OK;
-  const int nb = partial_blocks(rows, 16);
-  const uint32_t thr = bb_drop_threshold(drop_p);
-#define GO(T, N)                                                                                              \
-  hipLaunchKernelGGL((ln_bwd_kernel<T, N>), dim3(nb), dim3(256), 0, stream, (const T*)dy, (const T*)z, mean, \
-                     rstd, gamma, (T*)dz, (T*)dx, workspace, rows, drop_p, thr, bb_site_key(seed, offset), bb_step_salt(), \
-                     (const T*)dz_add)
-#define SW(T)                                                                     \
-  switch (H / 256) {                                                              \
-    case 1: GO(T, 1); break;                                                      \
-    case 2: GO(T, 2); break;                                                      \
-    case 3: GO(T, 3); break;                                                      \
-    case 4: GO(T, 4); break;                                                      \
-    default: bb_set_error("layernorm_bwd: H=%d unsupported", H); return BB_EUNSUPPORTED; \
-  }
-  if (dtype == BB_F32) { SW(float) } else if (dtype == BB_BF16) { SW(bf16_raw) } else {
-    bb_set_error("layernorm_bwd: dtype %d unsupported", dtype);
-    return BB_EUNSUPPORTED;
-  }
-#undef SW
-#undef GO
-  BB_CHECK_LAUNCH("layernorm_bwd");
-  if (dgamma || dbeta || dbias) launch_finalize(workspace, nb, 3, H, dgamma, dbeta, dbias, accumulate, stream);
-  BB_CHECK_LAUNCH("layernorm_bwd finalize");
-  return BB_OK;
-}
-
 // bf16 activations around an fp32 residual stream (see ln_res32_*_kernel): residual_dtype BB_F32 / BB_BF16 (ignored when
 // residual is NULL); y32 / z32 may be NULL (inference: no backward, or a consumer that only wants the bf16 copy)
 BEVBERT_API int bevbert_layernorm_res32_fwd(const void* x, const float* bias, const void* residual, int residual_dtype,
@@ -1313,20 +1288,14 @@ BEVBERT_API int bevbert_layernorm_res32_fwd(const void* x, const float* bias, co
   if (rows == 0) return BB_OK;
   const dim3 grid((rows + 3) / 4);
   const uint32_t thr = bb_drop_threshold(drop_p);
-#define GO(TR, N)                                                                                                       \
-  hipLaunchKernelGGL((ln_res32_fwd_kernel<TR, N>), grid, dim3(256), 0, stream, (const bf16_raw*)x, bias, (const TR*)residual, \
-                     gamma, beta, (bf16_raw*)y16, y32, z32, mean, rstd, rows, eps, drop_p, thr, bb_site_key(seed, offset),   \
-                     bb_step_salt())
-#define SW(TR)                \
-  switch (H / 256) {          \
-    case 1: GO(TR, 1); break; \
-    case 2: GO(TR, 2); break; \
-    case 3: GO(TR, 3); break; \
-    default: GO(TR, 4); break; \
-  }
-  if (residual != nullptr && residual_dtype == BB_BF16) { SW(bf16_raw) } else { SW(float) }
-#undef SW
-#undef GO
+  with_act_type(residual != nullptr && residual_dtype == BB_BF16 ? BB_BF16 : BB_F32, [&](auto t) {
+    using TR = decltype(t);
+    with_width<1, 2, 3, 4>(H, [&](auto nv) {
+      hipLaunchKernelGGL((ln_res32_fwd_kernel<TR, decltype(nv)::value>), grid, dim3(256), 0, stream, (const bf16_raw*)x, bias,
+                         (const TR*)residual, gamma, beta, (bf16_raw*)y16, y32, z32, mean, rstd, rows, eps, drop_p, thr,
+                         bb_site_key(seed, offset), bb_step_salt());
+    });
+  });
   BB_CHECK_LAUNCH("layernorm_res32_fwd");
   return BB_OK;
 }
@@ -1340,19 +1309,13 @@ BEVBERT_API int bevbert_layernorm_res32_bwd(const void* dy16, const float* dy32,
   BB_REQUIRE(H >= 256 && H % 256 == 0 && H / 256 <= 4, "layernorm_res32_bwd: H=%d must be 256, 512, 768 or 1024", H);
   BB_REQUIRE(dy16 != nullptr || dy32 != nullptr, "layernorm_res32_bwd: no output gradient");
   if (rows <= 0) return BB_OK;
-  const int nb = partial_blocks(rows, 16);
+  const int nb = colwise_blocks(rows);
   const uint32_t thr = bb_drop_threshold(drop_p);
-#define GO(N)                                                                                                          \
-  hipLaunchKernelGGL((ln_res32_bwd_kernel<N>), dim3(nb), dim3(256), 0, stream, (const bf16_raw*)dy16, dy32, z32, mean, rstd, \
-                     gamma, (float*)dz, (bf16_raw*)dx16, workspace, rows, drop_p, thr, bb_site_key(seed, offset), bb_step_salt(), \
-                     dz_dtype == BB_BF16 ? 1 : 0)
-  switch (H / 256) {
-    case 1: GO(1); break;
-    case 2: GO(2); break;
-    case 3: GO(3); break;
-    default: GO(4); break;
-  }
-#undef GO
+  with_width<1, 2, 3, 4>(H, [&](auto nv) {
+    hipLaunchKernelGGL((ln_res32_bwd_kernel<decltype(nv)::value>), dim3(nb), dim3(256), 0, stream, (const bf16_raw*)dy16, dy32, z32, mean,
+                       rstd, gamma, (float*)dz, (bf16_raw*)dx16, workspace, rows, drop_p, thr, bb_site_key(seed, offset),
+                       bb_step_salt(), dz_dtype == BB_BF16 ? 1 : 0);
+  });
   BB_CHECK_LAUNCH("layernorm_res32_bwd");
   if (dgamma || dbeta || dbias) launch_finalize(workspace, nb, 3, H, dgamma, dbeta, dbias, accumulate, stream);
   BB_CHECK_LAUNCH("layernorm_res32_bwd finalize");

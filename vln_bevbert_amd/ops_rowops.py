@@ -26,6 +26,44 @@ def embedding_grad_small(ids, d, sink, table_rows):
 
 
 # ----------------------------------------------------------------------------- K3 LayerNorm family
+def _ln_param_dests(gamma, beta, bias, H, dev):
+    """Where the gamma / beta / bias column sums of a LayerNorm backward go: ((dgamma, dbeta, dbias) tensors handed to the
+    kernel, (gamma, beta, bias) fp32 results to return through autograd, accumulate flag).  A parameter in the gradient arena
+    is accumulated into its sink (flag 1, nothing returned), a plain tensor gets a fresh fp32 vector (flag 0), a missing
+    one or a frozen bias (e.g. fix_lang_embedding) nothing."""
+    outs = []
+    for p in (gamma, beta, bias):
+        if p is None:
+            outs.append((None, None, 0))
+        elif p is bias and not getattr(p, "requires_grad", True):
+            outs.append((None, None, None))
+        elif _sink(p) is not None:
+            outs.append((_sink(p), None, 1))
+            _mark_touched(p)
+        else:
+            t = torch.empty(H, dtype=torch.float32, device=dev)
+            outs.append((t, t, 0))
+    (dg, rg, ag), (db, rb, ab), (dbi, rbi, abi) = outs
+    assert ag == ab and (bias is None or abi is None or abi == ag), "mixed arena / plain parameters in one LayerNorm"
+    return (dg, db, dbi), (rg, rb, rbi), ag
+
+
+def _ln_bwd_call(entry, head, mid, tail, dests, accumulate, rows, H, dev, ws=None):
+    """entry(*head, dgamma, dbeta, dbias, workspace, *mid, accumulate, *tail, stream).  Arena parameters (accumulate 1):
+    the kernel leaves its per-block partial sums in the scratch ring and the second stage of the reduction joins the step's
+    other pending reductions (ReduceQueue: one launch, off the critical path); otherwise both stages run here, through
+    the stream's workspace (``ws``: the caller's, when it has taken it already)."""
+    if accumulate == 1 and WgradStream.DEFER_FINALIZE and dev.type == "cuda":
+        nb = _partial_rows(rows)
+        part = RT.scratch.alloc(nb * 3 * H * 4, dev)
+        call(entry, *head, None, None, None, part, *mid, 1, *tail, stream())
+        ReduceQueue.add(part, nb, 3, H, tuple(ptr(d) for d in dests))
+    else:
+        if ws is None:
+            ws = RT.workspace(dev, lib.load().bevbert_colsum_workspace_floats(3 * H))
+        call(entry, *head, *(ptr(d) for d in dests), ptr(ws), *mid, accumulate, *tail, stream())
+
+
 class _BiasDropResLN(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, bias, residual, gamma, beta, eps, drop_p, inplace_z, post1=None, post2=None, return_z=False):
@@ -83,36 +121,15 @@ class _BiasDropResLN(torch.autograd.Function):
         dx = torch.empty_like(dy) if (drop_p > 0 and has_res) else None
         dev = dy.device
         ws = RT.workspace(dev, lib.load().bevbert_colsum_workspace_floats(3 * H))
-        outs = []
-        for p in (gamma, beta, bias):
-            if p is None:
-                outs.append((None, None, 0))
-            elif p is bias and not getattr(p, "requires_grad", True):
-                outs.append((None, None, None))          # a frozen bias (e.g. fix_lang_embedding): no gradient wanted
-            elif _sink(p) is not None:
-                outs.append((_sink(p), None, 1))
-                _mark_touched(p)
-            else:
-                t = torch.empty(H, dtype=torch.float32, device=dev)
-                outs.append((t, t, 0))
-        (dg, rg, ag), (db, rb, ab), (dbi, rbi, abi) = outs
-        assert ag == ab and (bias is None or abi is None or abi == ag), "mixed arena / plain parameters in one LayerNorm"
+        (dg, db, dbi), (rg, rb, rbi), ag = _ln_param_dests(gamma, beta, bias, H, dev)
         # without a residual branch only dx is needed (it is the single input gradient)
         if not has_res and drop_p > 0:
             dx, dz_ptr = dz, None
         else:
             dz_ptr = dz
-        if ag == 1 and WgradStream.DEFER_FINALIZE and dev.type == "cuda":
-            # arena parameters: the kernel leaves its per-block partial sums in the scratch ring; the second stage of
-            # the reduction joins the step's other pending reductions (ReduceQueue: one launch, off the critical path)
-            nb = _partial_rows(rows)
-            part = RT.scratch.alloc(nb * 3 * H * 4, dev)
-            call("bevbert_layernorm_bwd_add", ptr(dy), ptr(z), ptr(mean), ptr(rstd), ptr(_f32(gamma)), ptr(dz_ptr), ptr(dx),
-                 ptr(add), None, None, None, part, rows, H, dtype_code(dy), drop_p, seed, off, 1, stream())
-            ReduceQueue.add(part, nb, 3, H, (ptr(dg), ptr(db), ptr(dbi)))
-        else:
-            call("bevbert_layernorm_bwd_add", ptr(dy), ptr(z), ptr(mean), ptr(rstd), ptr(_f32(gamma)), ptr(dz_ptr), ptr(dx),
-                 ptr(add), ptr(dg), ptr(db), ptr(dbi), ptr(ws), rows, H, dtype_code(dy), drop_p, seed, off, ag, stream())
+        _ln_bwd_call("bevbert_layernorm_bwd_add", (ptr(dy), ptr(z), ptr(mean), ptr(rstd), ptr(_f32(gamma)), ptr(dz_ptr),
+                                                   ptr(dx), ptr(add)), (rows, H, dtype_code(dy), drop_p, seed, off), (),
+                     (dg, db, dbi), ag, rows, H, dev, ws)
         gx = dx if dx is not None else dz
         gres = dz if has_res else None
         cast = lambda r, p: None if r is None else r.to(p.dtype)
@@ -161,31 +178,10 @@ class _BiasDropResLN32(torch.autograd.Function):
         dy32 = dy32.contiguous() if dy32 is not None else None
         dz32 = torch.empty(z32.shape, dtype=res_dtype, device=dev)     # the residual's gradient, in the residual's dtype
         dx16 = torch.empty(z32.shape, dtype=torch.bfloat16, device=dev)
-        outs = []
-        for p in (gamma, beta, bias):
-            if p is None:
-                outs.append((None, None, 0))
-            elif p is bias and not getattr(p, "requires_grad", True):
-                outs.append((None, None, None))
-            elif _sink(p) is not None:
-                outs.append((_sink(p), None, 1))
-                _mark_touched(p)
-            else:
-                t = torch.empty(H, dtype=torch.float32, device=dev)
-                outs.append((t, t, 0))
-        (dg, rg, ag), (db, rb, ab), (dbi, rbi, abi) = outs
-        assert ag == ab and (bias is None or abi is None or abi == ag), "mixed arena / plain parameters in one LayerNorm"
-        if ag == 1 and WgradStream.DEFER_FINALIZE and dev.type == "cuda":
-            nb = _partial_rows(rows)
-            part = RT.scratch.alloc(nb * 3 * H * 4, dev)
-            call("bevbert_layernorm_res32_bwd", ptr(dy16), ptr(dy32), ptr(z32), ptr(mean), ptr(rstd), ptr(_f32(gamma)),
-                 ptr(dz32), ptr(dx16), None, None, None, part, rows, H, drop_p, seed, off, 1, dtype_code(dz32), stream())
-            ReduceQueue.add(part, nb, 3, H, (ptr(dg), ptr(db), ptr(dbi)))
-        else:
-            ws = RT.workspace(dev, lib.load().bevbert_colsum_workspace_floats(3 * H))
-            call("bevbert_layernorm_res32_bwd", ptr(dy16), ptr(dy32), ptr(z32), ptr(mean), ptr(rstd), ptr(_f32(gamma)),
-                 ptr(dz32), ptr(dx16), ptr(dg), ptr(db), ptr(dbi), ptr(ws), rows, H, drop_p, seed, off, ag, dtype_code(dz32),
-                 stream())
+        (dg, db, dbi), (rg, rb, rbi), ag = _ln_param_dests(gamma, beta, bias, H, dev)
+        _ln_bwd_call("bevbert_layernorm_res32_bwd", (ptr(dy16), ptr(dy32), ptr(z32), ptr(mean), ptr(rstd), ptr(_f32(gamma)),
+                                                     ptr(dz32), ptr(dx16)), (rows, H, drop_p, seed, off), (dtype_code(dz32),),
+                     (dg, db, dbi), ag, rows, H, dev)
         cast = lambda r, p: None if r is None else r.to(p.dtype)
         gres = dz32
         return dx16, cast(rbi, bias) if bias is not None else None, gres, cast(rg, gamma), cast(rb, beta), None, None
@@ -624,21 +620,13 @@ class _EmbedLN(torch.autograd.Function):
             _mark_touched(gamma); _mark_touched(beta)
             if styp is not None:
                 _mark_touched(typ)
-            if WgradStream.DEFER_FINALIZE:
-                nb = _partial_rows(rows)
-                part = RT.scratch.alloc(nb * 3 * H * 4, dy.device)
-                call("bevbert_layernorm_bwd", ptr(dy), ptr(z), ptr(mean), ptr(rstd), ptr(_f32(gamma)), ptr(dz), None,
-                     None, None, None, part, rows, H, dtype_code(dy), 0.0, 0, 0, 1, stream())
-                ReduceQueue.add(part, nb, 3, H, (ptr(sg), ptr(sb), ptr(styp)))
-            else:
-                call("bevbert_layernorm_bwd", ptr(dy), ptr(z), ptr(mean), ptr(rstd), ptr(_f32(gamma)), ptr(dz), None,
-                     ptr(sg), ptr(sb), ptr(styp), ptr(ws), rows, H, dtype_code(dy), 0.0, 0, 0, 1, stream())
             rg = rb = None
         else:
             rg = torch.empty(H, dtype=torch.float32, device=dy.device)
             rb = torch.empty(H, dtype=torch.float32, device=dy.device)
-            call("bevbert_layernorm_bwd", ptr(dy), ptr(z), ptr(mean), ptr(rstd), ptr(_f32(gamma)), ptr(dz), None,
-                 ptr(rg), ptr(rb), None, ptr(ws), rows, H, dtype_code(dy), 0.0, 0, 0, 0, stream())
+        _ln_bwd_call("bevbert_layernorm_bwd", (ptr(dy), ptr(z), ptr(mean), ptr(rstd), ptr(_f32(gamma)), ptr(dz), None),
+                     (rows, H, dtype_code(dy), 0.0, 0, 0), (), (sg, sb, styp) if sg is not None else (rg, rb, None),
+                     1 if sg is not None else 0, rows, H, dy.device, ws)
         dz2 = dz.reshape(rows, H)
         dzf = dz2          # (kept alive by the deferred closures below)
 
