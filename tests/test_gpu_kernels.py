@@ -1159,6 +1159,7 @@ def test_attention_packed_layouts(ops):
     o1.backward(do)
     o2.backward(do)
     assert torch.equal(qkv.grad[..., :H], q.grad) and torch.equal(qkv.grad[..., 2 * H:], v.grad)
+    assert torch.equal(qkv.grad[..., H:2 * H], k.grad)
 
 
 def test_attention_full_size_softmax_properties(ops):

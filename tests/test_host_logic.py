@@ -1161,3 +1161,42 @@ def test_quiet_gc_takes_the_long_lived_objects_out_of_the_collectors_reach():
         assert gc.get_freeze_count() > 1000 and gc.isenabled()
     finally:
         gc.unfreeze()
+
+
+def test_attention_gradient_destinations_have_the_operand_strides():
+    """ops_attention._grad_like: the backward kernels write dq / dk / dv with the OPERAND's strides, so the destination of a
+    dense tensor, of a column slice of a packed tensor (the hoisted K|V stride) and of a row-and-column slice has exactly
+    those strides and storage that covers its last element; an operand expanded over the batch is refused."""
+    from vln_bevbert_amd.ops_attention import _expanded, _grad_like
+    for dtype in (torch.float32, torch.bfloat16):
+        parent = torch.zeros(2, 5, 24, dtype=dtype)
+        for t in (parent, parent[..., 6:12], parent[..., 18:], parent[:, 1:4, 6:12], parent[1:, :, :6], parent[:1, :1, 6:12]):
+            g = _grad_like(t)
+            assert g.shape == t.shape and g.dtype == t.dtype and g.stride() == t.stride(), (t.stride(), g.stride())
+            last = sum((n - 1) * st for n, st in zip(g.shape, g.stride()))
+            assert g.storage_offset() + last < g.untyped_storage().nbytes() // g.element_size()
+            g.fill_(3)                          # every element is addressable and the slices of a packed gradient are views
+            assert float(g.sum()) == 3 * t.numel() and g[..., :3].data_ptr() == g.data_ptr()
+    assert _expanded(torch.zeros(5, 24).expand(2, 5, 24)) and not _expanded(parent[:1, :, 6:12].expand(1, 5, 6))
+    with pytest.raises(AssertionError):
+        _grad_like(torch.zeros(5, 24).expand(2, 5, 24)[..., 6:12])
+
+
+def test_hoisted_kv_holder_slot_is_claimed_once_and_sliced_at_the_packed_stride():
+    """_KVGradHolder: the first consumer of a layer's view claims its slice of the (B, Lk, layers * width) buffer."""
+    from vln_bevbert_amd.ops_gemm import _KVGradHolder
+    parent = torch.zeros(2, 5, 24)
+    h = _KVGradHolder(3, 6)
+    assert [h.claim(1), h.claim(1), h.claim(0), h.claim(1)] == [True, False, True, False]
+    assert h.grad_slice(1, parent[..., 6:12]).stride() == (3 * 6 * 5, 3 * 6, 1) and h.buf.shape == (2, 5, 18)
+
+
+def test_attention_stride_block_follows_the_header_order():
+    """ops_attention._strides: [ldq, ldk, ldv, ldo, bsq, bsk, bsv, bso] (include/bevbert_hip.h), every operand's own."""
+    from vln_bevbert_amd.ops_attention import _strides
+    q, o = torch.zeros(2, 7, 64), torch.zeros(2, 7, 64)
+    k = torch.zeros(2, 5, 3 * 64)[..., 64:128]
+    v = torch.zeros(2, 10, 5 * 64)[:, :5, 128:192]
+    assert list(_strides(q, k, v, o)) == [64, 192, 320, 64, 7 * 64, 5 * 192, 10 * 320, 7 * 64]
+    with pytest.raises(AssertionError):
+        _strides(q.transpose(1, 2), k, v, o)

@@ -18,6 +18,21 @@ def _strides(q, k, v, o):
     return arr
 
 
+def _expanded(t):
+    return any(st == 0 and n > 1 for n, st in zip(t.shape, t.stride()))
+
+
+def _grad_like(t):
+    """Uninitialised gradient destination of an attention operand.  The backward kernels write dq / dk / dv with the
+    OPERAND's strides (include/bevbert_hip.h), so the destination has exactly those strides and storage up to its last
+    element -- ``torch.empty_like`` makes a column slice of a packed tensor dense, which the kernels would overrun."""
+    if t.is_contiguous():
+        return torch.empty_like(t)
+    assert not _expanded(t), "a gradient cannot be written through an expanded operand"
+    span = 1 + sum((n - 1) * st for n, st in zip(t.shape, t.stride()))
+    return torch.empty(span, dtype=t.dtype, device=t.device).as_strided(t.shape, t.stride())
+
+
 def _bits_ahead(Lq, Lk, has_bias):
     return load().bevbert_attn_bits_ahead(Lq, Lk, int(has_bias))
 
@@ -27,6 +42,8 @@ class _Attention(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, mode, a, b_, c_, key_mask, bias, nh, drop_p, impl):
+        # (an operand expanded over the batch shares its rows: the kernels would write every batch's gradient to one place)
+        a, b_, c_ = (t.contiguous() if t is not None and _expanded(t) else t for t in (a, b_, c_))
         if mode == "self":
             H = a.shape[-1] // 3
             q, k, v = a[..., :H], a[..., H:2 * H], a[..., 2 * H:]
@@ -61,7 +78,10 @@ class _Attention(torch.autograd.Function):
              ptr(bits), bits_ready, stream())
         ctx.save_for_backward(a, b_, c_, key_mask, bias, o, lse, bits)
         ctx.cfg = (mode, nh, float(drop_p), RT.seed, off, impl, scale)
-        ctx.kv_slot = getattr(b_, "_kv_grad_slot", None) if mode == "cross" else None     # see hoisted_kv
+        # hoisted_kv: the first attention that consumes a layer's K|V view writes its gradient straight into the view's
+        # slot of the shared buffer; any further consumer of the same view keeps a buffer of its own, which autograd adds
+        slot = getattr(b_, "_kv_grad_slot", None) if mode == "cross" and ctx.needs_input_grad[2] else None
+        ctx.kv_slot = slot if slot is not None and slot[0].claim(slot[1]) else None
         ctx.bias_slot = getattr(bias, "_dbias_slot", None) if bias is not None else None    # see graph_bias
         return o
 
@@ -73,21 +93,22 @@ class _Attention(torch.autograd.Function):
         if mode == "self":
             H = a.shape[-1] // 3
             q, k, v = a[..., :H], a[..., H:2 * H], a[..., 2 * H:]
-            da = torch.empty_like(a)
+            da = _grad_like(a)
             dq, dk, dv = da[..., :H], da[..., H:2 * H], da[..., 2 * H:]
             grads = (da, None, None)
         elif mode == "cross":
             H = a.shape[-1]
             q, k, v = a, b_[..., :H], b_[..., H:]
-            dq = torch.empty_like(a)
+            dq = _grad_like(a)
             # K/V projected for all layers of an encoder at once (hoisted_kv): the gradient goes straight into this
             # layer's column slice of the shared (B, Lk, layers * 2H) buffer, which feeds ONE input-gradient GEMM
-            dkv = ctx.kv_slot[0].grad_slice(ctx.kv_slot[1], b_) if ctx.kv_slot is not None else torch.empty_like(b_)
+            dkv = ctx.kv_slot[0].grad_slice(ctx.kv_slot[1], b_) if ctx.kv_slot is not None else _grad_like(b_)
+            assert dkv.stride() == b_.stride(), "the hoisted K|V view is a column slice of its (B, Lk, layers * 2H) tensor"
             dk, dv = dkv[..., :H], dkv[..., H:]
             grads = (dq, dkv, None)
         else:
             q, k, v = a, b_, c_
-            dq, dk, dv = torch.empty_like(a), torch.empty_like(b_), torch.empty_like(c_)
+            dq, dk, dv = _grad_like(a), _grad_like(b_), _grad_like(c_)
             grads = (dq, dk, dv)
         B, Lq, Lk = q.shape[0], q.shape[1], k.shape[1]
         delta = torch.empty(B, nh, Lq, dtype=torch.float32, device=q.device)

@@ -386,10 +386,19 @@ HOIST_KV = _os.environ.get("BEVBERT_HOIST_KV", "1") == "1"      # A/B knob
 
 class _KVGradHolder:
     """The (B, Lk, layers * 2H) gradient buffer of a hoisted K/V projection, allocated when the first attention backward
-    asks for its slice."""
+    asks for its slice.  A layer's slice takes the gradient of ONE consumer of that layer's view (``claim``): two
+    backwards writing the same slice would leave the second gradient, which autograd would then add to itself."""
 
     def __init__(self, n_layers, width):
         self.n, self.width, self.buf = n_layers, width, None
+        self._claimed = set()
+
+    def claim(self, layer):
+        """True for the first caller per layer: that one writes ``grad_slice(layer)``."""
+        if layer in self._claimed:
+            return False
+        self._claimed.add(layer)
+        return True
 
     def grad_slice(self, layer, like):
         if self.buf is None:
@@ -415,6 +424,7 @@ class _HoistedKV(torch.autograd.Function):
                   pw.compute.shape[0], pw.compute.shape[1])
         width = y.shape[-1] // n_layers
         ctx.holder = _KVGradHolder(n_layers, width)
+        ctx.set_materialize_grads(False)      # a layer nobody consumed arrives as None (zeroed in place), not as dense zeros
         return tuple(y[..., i * width:(i + 1) * width] for i in range(n_layers))
 
     @staticmethod
