@@ -116,6 +116,63 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, co
 //   per-column partial sums of dy*xhat (dgamma), dy (dbeta), dx (dbias) -> partials[block][3][H]
 // Persistent-style grid: each wave strides over rows and keeps its column partials in registers.
 // =============================================================================================
+// The arithmetic of one float4 chunk of a row, shared by every LayerNorm backward kernel of this file (the plain one,
+// the fp32-stream one and its load-ahead form): one place for what must stay bit-identical between them.
+// First half: xhat of the chunk, its terms of the dgamma / dbeta column partials, d <- gamma * dy, the row sums' terms.
+__device__ __forceinline__ void ln_bwd_chunk_reduce(float4& d, const float4 zz, float mu, float rs, const float4 g, float4& xh,
+                                                    float4& ag, float4& ab, float& s1, float& s2) {
+  xh = make_float4((zz.x - mu) * rs, (zz.y - mu) * rs, (zz.z - mu) * rs, (zz.w - mu) * rs);
+  ag.x += d.x * xh.x; ag.y += d.y * xh.y; ag.z += d.z * xh.z; ag.w += d.w * xh.w;
+  ab.x += d.x; ab.y += d.y; ab.z += d.z; ab.w += d.w;
+  d.x *= g.x; d.y *= g.y; d.z *= g.z; d.w *= g.w;
+  s1 += (d.x + d.y) + (d.z + d.w);
+  s2 += (d.x * xh.x + d.y * xh.y) + (d.z * xh.z + d.w * xh.w);
+}
+// Second half, with s1 / s2 the row means: the chunk of dz ...
+__device__ __forceinline__ float4 ln_bwd_chunk_dz(const float4 d, const float4 xh, float rs, float s1, float s2) {
+  float4 o;
+  o.x = rs * (d.x - s1 - xh.x * s2);
+  o.y = rs * (d.y - s1 - xh.y * s2);
+  o.z = rs * (d.z - s1 - xh.z * s2);
+  o.w = rs * (d.w - s1 - xh.w * s2);
+  return o;
+}
+// ... and of dx: dz through the forward's dropout mask (elem = the chunk's first element index in the tensor)
+__device__ __forceinline__ float4 ln_bwd_chunk_drop(float4 o, uint32_t elem, uint32_t drop_key, uint32_t drop_thr,
+                                                  float keep_scale) {
+  const uint32_t pr = elem >> 1;
+  const uint32_t b0 = bb_pair_bits(drop_key, pr), b1 = bb_pair_bits(drop_key, pr + 1);
+  o.x = bb_keep_lo(b0, drop_thr) ? o.x * keep_scale : 0.f;
+  o.y = bb_keep_hi(b0, drop_thr) ? o.y * keep_scale : 0.f;
+  o.z = bb_keep_lo(b1, drop_thr) ? o.z * keep_scale : 0.f;
+  o.w = bb_keep_hi(b1, drop_thr) ? o.w * keep_scale : 0.f;
+  return o;
+}
+// The end of these kernels: the four waves' column partials folded through LDS in wave order into partials[block][3][H]
+template <int NV>
+__device__ __forceinline__ void ln_bwd_store_partials(float4 (&s_red)[3][4][NV * 64], const float4 (&ag)[NV],
+                                                      const float4 (&ab)[NV], const float4 (&ax)[NV],
+                                                      float* __restrict__ partials, int lane, int wave) {
+  constexpr int H = NV * 256;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    s_red[0][wave][i * 64 + lane] = ag[i];
+    s_red[1][wave][i * 64 + lane] = ab[i];
+    s_red[2][wave][i * 64 + lane] = ax[i];
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < 3 * NV * 64; k += 256) {
+    const int which = k / (NV * 64), j = k % (NV * 64);
+    float4 a = s_red[which][0][j];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) {
+      const float4 t = s_red[which][w][j];
+      a.x += t.x; a.y += t.y; a.z += t.z; a.w += t.w;
+    }
+    *reinterpret_cast<float4*>(partials + ((size_t)blockIdx.x * 3 + which) * H + j * 4) = a;
+  }
+}
+
 template <typename T, int NV>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ z,
                                                      const float* __restrict__ mean, const float* __restrict__ rstd,
@@ -144,56 +201,62 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
       const int col = (i * 64 + lane) * 4;
       d[i] = ld4<T>(dy + (size_t)row * H + col);
       const float4 zz = ld4<T>(z + (size_t)row * H + col);
-      xh[i] = make_float4((zz.x - mu) * rs, (zz.y - mu) * rs, (zz.z - mu) * rs, (zz.w - mu) * rs);
-      ag[i].x += d[i].x * xh[i].x; ag[i].y += d[i].y * xh[i].y; ag[i].z += d[i].z * xh[i].z; ag[i].w += d[i].w * xh[i].w;
-      ab[i].x += d[i].x; ab[i].y += d[i].y; ab[i].z += d[i].z; ab[i].w += d[i].w;
-      d[i].x *= g[i].x; d[i].y *= g[i].y; d[i].z *= g[i].z; d[i].w *= g[i].w;
-      s1 += (d[i].x + d[i].y) + (d[i].z + d[i].w);
-      s2 += (d[i].x * xh[i].x + d[i].y * xh[i].y) + (d[i].z * xh[i].z + d[i].w * xh[i].w);
+      ln_bwd_chunk_reduce(d[i], zz, mu, rs, g[i], xh[i], ag[i], ab[i], s1, s2);
     }
     s1 = wave_sum(s1) * (1.0f / H);
     s2 = wave_sum(s2) * (1.0f / H);
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const int col = (i * 64 + lane) * 4;
-      float4 o;
-      o.x = rs * (d[i].x - s1 - xh[i].x * s2);
-      o.y = rs * (d[i].y - s1 - xh[i].y * s2);
-      o.z = rs * (d[i].z - s1 - xh[i].z * s2);
-      o.w = rs * (d[i].w - s1 - xh[i].w * s2);
+      float4 o = ln_bwd_chunk_dz(d[i], xh[i], rs, s1, s2);
       if (dz_add != nullptr) {       // z has a second consumer (pre-norm residual stream): its gradient joins here
         const float4 e = ld4<T>(dz_add + (size_t)row * H + col);
         o.x += e.x; o.y += e.y; o.z += e.z; o.w += e.w;
       }
       if (dz_out != nullptr) st4<T>(dz_out + (size_t)row * H + col, o);
-      if (drop_p > 0.f) {
-        const uint32_t pr = ((uint32_t)row * H + col) >> 1;
-        const uint32_t b0 = bb_pair_bits(drop_key, pr), b1 = bb_pair_bits(drop_key, pr + 1);
-        o.x = bb_keep_lo(b0, drop_thr) ? o.x * keep_scale : 0.f;
-        o.y = bb_keep_hi(b0, drop_thr) ? o.y * keep_scale : 0.f;
-        o.z = bb_keep_lo(b1, drop_thr) ? o.z * keep_scale : 0.f;
-        o.w = bb_keep_hi(b1, drop_thr) ? o.w * keep_scale : 0.f;
-      }
+      if (drop_p > 0.f) o = ln_bwd_chunk_drop(o, (uint32_t)row * H + col, drop_key, drop_thr, keep_scale);
       if (dx_out != nullptr) st4<T>(dx_out + (size_t)row * H + col, o);
       ax[i].x += o.x; ax[i].y += o.y; ax[i].z += o.z; ax[i].w += o.w;
     }
   }
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    s_red[0][wave][i * 64 + lane] = ag[i];
-    s_red[1][wave][i * 64 + lane] = ab[i];
-    s_red[2][wave][i * 64 + lane] = ax[i];
+  ln_bwd_store_partials<NV>(s_red, ag, ab, ax, partials, lane, wave);
+}
+
+// ---- helpers of the fp32-stream backward with the NEXT row's loads in flight (ln_res32_bwd_ahead_kernel) ----------
+// A row's operands are held as they leave memory (16-bit types still packed): a conversion issued with the loads
+// would wait for them.
+template <typename T> struct raw4;
+template <> struct raw4<float> {
+  typedef float4 type;
+  static __device__ __forceinline__ float4 ld(const float* p) { return *reinterpret_cast<const float4*>(p); }
+  static __device__ __forceinline__ float4 f32(float4 v) { return v; }
+};
+template <> struct raw4<bf16_raw> {
+  typedef uint2 type;
+  static __device__ __forceinline__ uint2 ld(const bf16_raw* p) { return *reinterpret_cast<const uint2*>(p); }
+  static __device__ __forceinline__ float4 f32(uint2 u) {      // as ld4<bf16_raw>
+    return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
+                       __uint_as_float(u.y & 0xffff0000u));
   }
-  __syncthreads();
-  for (int k = threadIdx.x; k < 3 * NV * 64; k += 256) {
-    const int which = k / (NV * 64), j = k % (NV * 64);
-    float4 a = s_red[which][0][j];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) {
-      const float4 t = s_red[which][w][j];
-      a.x += t.x; a.y += t.y; a.z += t.z; a.w += t.w;
-    }
-    *reinterpret_cast<float4*>(partials + ((size_t)blockIdx.x * 3 + which) * H + j * 4) = a;
+};
+// apply(row, buffer) for row0, row0 + stride, ... < rows: two register buffers in turn, the next row's fill(buffer, row)
+// issued before the current row's apply()
+template <typename Row, typename F, typename A>
+__device__ __forceinline__ void walk_rows_ahead(int row, int rows, int stride, F&& fill, A&& apply) {
+  if (row >= rows) return;
+  Row a, b;
+  fill(a, row);
+  for (;;) {
+    int next = row + stride;
+    if (next < rows) fill(b, next);
+    apply(row, a);
+    if (next >= rows) break;
+    row = next;
+    next = row + stride;
+    if (next < rows) fill(a, next);
+    apply(row, b);
+    if (next >= rows) break;
+    row = next;
   }
 }
 
@@ -310,56 +373,140 @@ __global__ __launch_bounds__(256) void ln_res32_bwd_kernel(const bf16_raw* __res
         d[i].x += e.x; d[i].y += e.y; d[i].z += e.z; d[i].w += e.w;
       }
       const float4 zz = ld4<float>(z + (size_t)row * H + col);
-      xh[i] = make_float4((zz.x - mu) * rs, (zz.y - mu) * rs, (zz.z - mu) * rs, (zz.w - mu) * rs);
-      ag[i].x += d[i].x * xh[i].x; ag[i].y += d[i].y * xh[i].y; ag[i].z += d[i].z * xh[i].z; ag[i].w += d[i].w * xh[i].w;
-      ab[i].x += d[i].x; ab[i].y += d[i].y; ab[i].z += d[i].z; ab[i].w += d[i].w;
-      d[i].x *= g[i].x; d[i].y *= g[i].y; d[i].z *= g[i].z; d[i].w *= g[i].w;
-      s1 += (d[i].x + d[i].y) + (d[i].z + d[i].w);
-      s2 += (d[i].x * xh[i].x + d[i].y * xh[i].y) + (d[i].z * xh[i].z + d[i].w * xh[i].w);
+      ln_bwd_chunk_reduce(d[i], zz, mu, rs, g[i], xh[i], ag[i], ab[i], s1, s2);
     }
     s1 = wave_sum(s1) * (1.0f / H);
     s2 = wave_sum(s2) * (1.0f / H);
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const int col = (i * 64 + lane) * 4;
-      float4 o;
-      o.x = rs * (d[i].x - s1 - xh[i].x * s2);
-      o.y = rs * (d[i].y - s1 - xh[i].y * s2);
-      o.z = rs * (d[i].z - s1 - xh[i].z * s2);
-      o.w = rs * (d[i].w - s1 - xh[i].w * s2);
+      float4 o = ln_bwd_chunk_dz(d[i], xh[i], rs, s1, s2);
       if (dz_out != nullptr) {
         if (dz_bf16) st4<bf16_raw>(reinterpret_cast<bf16_raw*>(dz_out) + (size_t)row * H + col, o);
         else st4<float>(dz_out + (size_t)row * H + col, o);
       }
-      if (drop_p > 0.f) {
-        const uint32_t pr = ((uint32_t)row * H + col) >> 1;
-        const uint32_t b0 = bb_pair_bits(drop_key, pr), b1 = bb_pair_bits(drop_key, pr + 1);
-        o.x = bb_keep_lo(b0, drop_thr) ? o.x * keep_scale : 0.f;
-        o.y = bb_keep_hi(b0, drop_thr) ? o.y * keep_scale : 0.f;
-        o.z = bb_keep_lo(b1, drop_thr) ? o.z * keep_scale : 0.f;
-        o.w = bb_keep_hi(b1, drop_thr) ? o.w * keep_scale : 0.f;
-      }
+      if (drop_p > 0.f) o = ln_bwd_chunk_drop(o, (uint32_t)row * H + col, drop_key, drop_thr, keep_scale);
       if (dx_out != nullptr) st4<bf16_raw>(dx_out + (size_t)row * H + col, o);
       ax[i].x += o.x; ax[i].y += o.y; ax[i].z += o.z; ax[i].w += o.w;
     }
   }
+  ln_bwd_store_partials<NV>(s_red, ag, ab, ax, partials, lane, wave);
+}
+
+// The same with the NEXT row's loads in flight.  Up to 512 workgroups (5 120 rows) a launch has two waves per SIMD and a
+// wave two or three rows, each a dependent load -> reduce -> store chain: the kernel is latency-bound and the registers for
+// a second row are free.  The host picks this form there (ln_res32_bwd_loads_ahead); larger launches need four waves per
+// SIMD (<= 128 VGPRs) and keep the kernel above.  Which rows a wave takes, the order in which it adds them into its column
+// partials and the arithmetic of a row (ln_bwd_chunk_*) are those of the kernel above.
+template <int NV> struct LnRes32BwdRow {
+  uint2 d16[NV];          // dy16, packed (when there is one)
+  float4 d32[NV], z[NV];  // dy32 (when there is one), z
+  float mu, rs;
+};
+template <int NV>
+__global__ __launch_bounds__(256) void ln_res32_bwd_ahead_kernel(const bf16_raw* __restrict__ dy16, const float* __restrict__ dy32,
+                                                                 const float* __restrict__ z, const float* __restrict__ mean,
+                                                                 const float* __restrict__ rstd, const float* __restrict__ gamma,
+                                                                 float* __restrict__ dz_out, bf16_raw* __restrict__ dx_out,
+                                                                 float* __restrict__ partials, int rows, float drop_p,
+                                                                 uint32_t drop_thr, uint32_t drop_key,
+                                                                 const uint32_t* __restrict__ salt, int dz_bf16) {
+  // dz_bf16: dz_out is a bf16 tensor (the residual was a bf16 tensor -- where an fp32 residual stream starts)
+  constexpr int H = NV * 256;
+  if (drop_p > 0.f) drop_key = bb_salted(drop_key, salt);
+  __shared__ float4 s_red[3][4][NV * 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float keep_scale = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
+  float4 ag[NV], ab[NV], ax[NV];
+  float4 g[NV];
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
-    s_red[0][wave][i * 64 + lane] = ag[i];
-    s_red[1][wave][i * 64 + lane] = ab[i];
-    s_red[2][wave][i * 64 + lane] = ax[i];
+    ag[i] = ab[i] = ax[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    g[i] = *reinterpret_cast<const float4*>(gamma + (i * 64 + lane) * 4);
   }
-  __syncthreads();
-  for (int k = threadIdx.x; k < 3 * NV * 64; k += 256) {
-    const int which = k / (NV * 64), j = k % (NV * 64);
-    float4 a = s_red[which][0][j];
+  auto fill = [&](LnRes32BwdRow<NV>& r, int row) __attribute__((always_inline)) {
+    r.mu = mean[row];
+    r.rs = rstd[row];
 #pragma unroll
-    for (int w = 1; w < 4; ++w) {
-      const float4 t = s_red[which][w][j];
-      a.x += t.x; a.y += t.y; a.z += t.z; a.w += t.w;
+    for (int i = 0; i < NV; ++i) {
+      const size_t at = (size_t)row * H + (i * 64 + lane) * 4;
+      if (dy16 != nullptr) r.d16[i] = raw4<bf16_raw>::ld(dy16 + at);
+      if (dy32 != nullptr) r.d32[i] = raw4<float>::ld(dy32 + at);
+      r.z[i] = raw4<float>::ld(z + at);
     }
-    *reinterpret_cast<float4*>(partials + ((size_t)blockIdx.x * 3 + which) * H + j * 4) = a;
+  };
+  auto apply = [&](int row, const LnRes32BwdRow<NV>& r) __attribute__((always_inline)) {
+    const float mu = r.mu, rs = r.rs;
+    float4 d[NV], xh[NV];
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      d[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (dy16 != nullptr) d[i] = raw4<bf16_raw>::f32(r.d16[i]);
+      if (dy32 != nullptr) {
+        const float4 e = r.d32[i];
+        d[i].x += e.x; d[i].y += e.y; d[i].z += e.z; d[i].w += e.w;
+      }
+      const float4 zz = r.z[i];
+      ln_bwd_chunk_reduce(d[i], zz, mu, rs, g[i], xh[i], ag[i], ab[i], s1, s2);
+    }
+    s1 = wave_sum(s1) * (1.0f / H);
+    s2 = wave_sum(s2) * (1.0f / H);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int col = (i * 64 + lane) * 4;
+      float4 o = ln_bwd_chunk_dz(d[i], xh[i], rs, s1, s2);
+      if (dz_out != nullptr) {
+        if (dz_bf16) st4<bf16_raw>(reinterpret_cast<bf16_raw*>(dz_out) + (size_t)row * H + col, o);
+        else st4<float>(dz_out + (size_t)row * H + col, o);
+      }
+      if (drop_p > 0.f) o = ln_bwd_chunk_drop(o, (uint32_t)row * H + col, drop_key, drop_thr, keep_scale);
+      if (dx_out != nullptr) st4<bf16_raw>(dx_out + (size_t)row * H + col, o);
+      ax[i].x += o.x; ax[i].y += o.y; ax[i].z += o.z; ax[i].w += o.w;
+    }
+  };
+  walk_rows_ahead<LnRes32BwdRow<NV>>(blockIdx.x * 4 + wave, rows, gridDim.x * 4, fill, apply);
+  ln_bwd_store_partials<NV>(s_red, ag, ab, ax, partials, lane, wave);
+}
+
+// Loads through global-address-space pointers (global_load: a pointer read out of a task record is otherwise a flat one,
+// whose loads also wait on the LDS counter and whose stores fence later loads)
+typedef float bb_f4v __attribute__((ext_vector_type(4)));
+typedef uint32_t bb_u2v __attribute__((ext_vector_type(2)));
+#define BB_GLOBAL __attribute__((address_space(1)))
+template <typename T> __device__ __forceinline__ float4 gld4(const BB_GLOBAL T* p);
+template <> __device__ __forceinline__ float4 gld4<float>(const BB_GLOBAL float* p) {
+  const bb_f4v v = *reinterpret_cast<const BB_GLOBAL bb_f4v*>(p);
+  return make_float4(v[0], v[1], v[2], v[3]);
+}
+template <> __device__ __forceinline__ float4 gld4<bf16_raw>(const BB_GLOBAL bf16_raw* p) {
+  const bb_u2v u = *reinterpret_cast<const BB_GLOBAL bb_u2v*>(p);
+  return make_float4(__uint_as_float(u[0] << 16), __uint_as_float(u[0] & 0xffff0000u), __uint_as_float(u[1] << 16),
+                     __uint_as_float(u[1] & 0xffff0000u));
+}
+
+// p[b0 * stride] + p[(b0 + 16) * stride] + ... over b < nblocks, as ONE running fp32 sum in ascending b.  Only the loads
+// are batched (16, then 4, then 1 in flight; one at a time, 32 - 64 dependent round trips per thread, the finalize
+// kernels ran at 0.38 of the streaming rate): the adds and their order are those of the plain loop.
+template <int U>
+__device__ __forceinline__ void strided_sum_batches(const BB_GLOBAL float* __restrict__ p, int& b, int nblocks, size_t stride,
+                                                    float& s) {
+  for (; b + (U - 1) * 16 < nblocks; b += U * 16) {
+    float v[U];
+#pragma unroll
+    for (int k = 0; k < U; ++k) v[k] = p[(size_t)(b + k * 16) * stride];
+#pragma unroll
+    for (int k = 0; k < U; ++k) s += v[k];
   }
+}
+__device__ __forceinline__ float strided_sum16(const float* p_, int b0, int nblocks, size_t stride) {
+  const BB_GLOBAL float* __restrict__ p = (const BB_GLOBAL float*)p_;
+  float s = 0.f;
+  int b = b0;
+  strided_sum_batches<16>(p, b, nblocks, stride, s);
+  strided_sum_batches<4>(p, b, nblocks, stride, s);
+  strided_sum_batches<1>(p, b, nblocks, stride, s);
+  return s;
 }
 
 // out_w[c] (+)= sum_b partials[b][w][c] for every w with a non-null output.  Block = 64 columns x 16 partial groups:
@@ -374,8 +521,7 @@ __global__ __launch_bounds__(1024) void colsum_finalize_kernel(const float* __re
   const int tx = threadIdx.x, ty = threadIdx.y;
   const int c = blockIdx.x * 64 + tx;
   float s = 0.f;
-  if (c < C)
-    for (int b = ty; b < nblocks; b += 16) s += partials[((size_t)b * nwhich + which) * C + c];
+  if (c < C) s = strided_sum16(partials + (size_t)which * C + c, ty, nblocks, (size_t)nwhich * C);
   sh[ty][tx] = s;
   __syncthreads();
   if (ty == 0 && c < C) {
@@ -407,8 +553,7 @@ __global__ __launch_bounds__(1024) void multi_finalize_kernel(const FinalizeTask
   const FinalizeTask t = tasks[blockIdx.x];
   const int tx = threadIdx.x, ty = threadIdx.y;
   float s = 0.f;
-  if (tx < t.ncols)
-    for (int b = ty; b < t.nblocks; b += 16) s += t.partials[(size_t)b * t.row_stride + t.col0 + tx];
+  if (tx < t.ncols) s = strided_sum16(t.partials + t.col0 + tx, ty, t.nblocks, (size_t)t.row_stride);
   sh[ty][tx] = s;
   __syncthreads();
   if (ty == 0 && tx < t.ncols) {
@@ -566,17 +711,64 @@ __global__ __launch_bounds__(192) void gather_wsum_kernel(const T* __restrict__ 
 
 // sink[i] += sum_s partials[s][i]: the reduction step of the host-side split-K weight-gradient GEMMs, fused with the
 // accumulation into the fp32 gradient arena (replaces a torch sum + add_ pair).  S is small (<= 32).
+// Both folds below are latency times a trip count, not bandwidth, when a thread has one load in flight (the first form:
+// 16 x (1 + S) dependent round trips per 4096-group task).  accum_fold keeps ACCUM_U elements x ACCUM_SC slices in flight:
+// every load of a batch is issued before the first add, through global-address-space pointers (a pointer read out of a
+// task record is otherwise a flat one, and the store of one element would fence the loads of the next).  The adds of an
+// element stay ((sink + p0) + p1) + ... + p(S-1), whatever S: slices beyond the last full batch are taken one at a time
+// in the same order.  Elements past the end are clamped to the last one for the loads and not stored.
+#define ACCUM_U 4
+#define ACCUM_SC 4
+// sink[i] += sum_s part[s * stride4 + i] for the float4 groups i = first, first + step, ... < n4
+template <typename T>
+__device__ __forceinline__ void accum_fold(const T* part_, float* sink_, size_t stride4, size_t n4, int S, size_t first,
+                                           size_t step) {
+  const BB_GLOBAL T* __restrict__ part = (const BB_GLOBAL T*)part_;
+  BB_GLOBAL float* __restrict__ sink = (BB_GLOBAL float*)sink_;
+  for (size_t i = first; i < n4; i += ACCUM_U * step) {
+    size_t idx[ACCUM_U];
+    float4 acc[ACCUM_U];
+#pragma unroll
+    for (int u = 0; u < ACCUM_U; ++u) {
+      idx[u] = i + u * step < n4 ? i + u * step : n4 - 1;
+      acc[u] = gld4<float>(sink + idx[u] * 4);
+    }
+    int s = 0;
+    for (; s + ACCUM_SC <= S; s += ACCUM_SC) {
+      float4 v[ACCUM_SC][ACCUM_U];
+#pragma unroll
+      for (int k = 0; k < ACCUM_SC; ++k)
+#pragma unroll
+        for (int u = 0; u < ACCUM_U; ++u) v[k][u] = gld4<T>(part + ((size_t)(s + k) * stride4 + idx[u]) * 4);
+#pragma unroll
+      for (int k = 0; k < ACCUM_SC; ++k)
+#pragma unroll
+        for (int u = 0; u < ACCUM_U; ++u) {
+          acc[u].x += v[k][u].x; acc[u].y += v[k][u].y; acc[u].z += v[k][u].z; acc[u].w += v[k][u].w;
+        }
+    }
+    for (; s < S; ++s) {
+      float4 v[ACCUM_U];
+#pragma unroll
+      for (int u = 0; u < ACCUM_U; ++u) v[u] = gld4<T>(part + ((size_t)s * stride4 + idx[u]) * 4);
+#pragma unroll
+      for (int u = 0; u < ACCUM_U; ++u) {
+        acc[u].x += v[u].x; acc[u].y += v[u].y; acc[u].z += v[u].z; acc[u].w += v[u].w;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < ACCUM_U; ++u)
+      if (i + u * step < n4) {
+        const bb_f4v o = {acc[u].x, acc[u].y, acc[u].z, acc[u].w};
+        *reinterpret_cast<BB_GLOBAL bb_f4v*>(sink + idx[u] * 4) = o;
+      }
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void accum_partials_kernel(const T* __restrict__ partials, float* __restrict__ sink,
                                                              int S, size_t n4) {
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-    float4 acc = *reinterpret_cast<const float4*>(sink + i * 4);
-    for (int s = 0; s < S; ++s) {
-      const float4 v = ld4<T>(partials + ((size_t)s * n4 + i) * 4);
-      acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-    }
-    *reinterpret_cast<float4*>(sink + i * 4) = acc;
-  }
+  accum_fold<T>(partials, sink, n4, n4, S, (size_t)blockIdx.x * 256 + threadIdx.x, (size_t)gridDim.x * 256);
 }
 
 // Batched form of accum_partials_kernel: one launch folds the split-K partial products of EVERY weight-gradient GEMM of
@@ -591,15 +783,7 @@ struct AccumTask {
 };
 template <typename T>
 __device__ __forceinline__ void accum_task(const AccumTask& t) {
-  const T* part = (const T*)t.partials;
-  for (unsigned i = threadIdx.x; i < t.n4; i += 256) {
-    float4 acc = *reinterpret_cast<const float4*>(t.sink + (size_t)i * 4);
-    for (int s = 0; s < t.S; ++s) {
-      const float4 v = ld4<T>(part + ((size_t)s * t.n4_total + t.off4 + i) * 4);
-      acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-    }
-    *reinterpret_cast<float4*>(t.sink + (size_t)i * 4) = acc;
-  }
+  accum_fold<T>((const T*)t.partials + (size_t)t.off4 * 4, t.sink, t.n4_total, t.n4, t.S, threadIdx.x, 256);
 }
 __global__ __launch_bounds__(256) void multi_accum_kernel(const AccumTask* __restrict__ tasks) {
   const AccumTask t = tasks[blockIdx.x];
@@ -1189,7 +1373,8 @@ BEVBERT_API int bevbert_embed_sum_layernorm_fwd(const int64_t* ids, const void* 
 // an uneven last round --, 2 048: 69.2), the bf16 LayerNorm backward and the GELU backward do not care (31.4 -> 30.0,
 // 105.4 -> 104.1 us), the bare column sums lose 0.8 us (r06al).  Below 8 192 rows the kernels are latency-bound -- a wave walks its rows one after the other, every row
 // a dependent load -> reduce -> store chain -- and 10 rows per block (two or three per wave; 512 blocks for the 5 120 text
-// rows instead of 320) shortens that chain.  BEVBERT_ROWS_PER_BLOCK overrides (A/B measurements).
+// rows instead of 320) shortens that chain; up to 512 blocks the fp32-stream LayerNorm backward also loads a wave's next
+// row while it reduces the current one (ln_res32_bwd_loads_ahead).  BEVBERT_ROWS_PER_BLOCK overrides (A/B measurements).
 static int colwise_max_blocks() {
   static const int cap = [] { const char* v = getenv("BEVBERT_COLWISE_MAX_BLOCKS"); const int c = v ? atoi(v) : 0; return c > 0 ? c : 1024; }();
   return cap;
@@ -1201,6 +1386,10 @@ static int colwise_blocks(int rows) {
   if (nb > colwise_max_blocks()) nb = colwise_max_blocks();
   return nb < 1 ? 1 : nb;
 }
+
+// ln_res32_bwd_ahead_kernel (the next row's loads in flight, ~190 VGPRs at H = 768) where its workgroups are all resident
+// at two waves per SIMD: up to 512 of them on the 256 CUs, i.e. up to 5 120 rows.  Larger launches keep the plain kernel.
+static bool ln_res32_bwd_loads_ahead(int nblocks) { return nblocks <= 512; }
 
 // row groups of a purely elementwise row kernel (no partial rows to bound): 8 rows each, at most 4096 groups
 static int elementwise_row_groups(int rows) {
@@ -1312,7 +1501,8 @@ BEVBERT_API int bevbert_layernorm_res32_bwd(const void* dy16, const float* dy32,
   const int nb = colwise_blocks(rows);
   const uint32_t thr = bb_drop_threshold(drop_p);
   with_width<1, 2, 3, 4>(H, [&](auto nv) {
-    hipLaunchKernelGGL((ln_res32_bwd_kernel<decltype(nv)::value>), dim3(nb), dim3(256), 0, stream, (const bf16_raw*)dy16, dy32, z32, mean,
+    auto* kernel = ln_res32_bwd_loads_ahead(nb) ? ln_res32_bwd_ahead_kernel<decltype(nv)::value> : ln_res32_bwd_kernel<decltype(nv)::value>;
+    hipLaunchKernelGGL(kernel, dim3(nb), dim3(256), 0, stream, (const bf16_raw*)dy16, dy32, z32, mean,
                        rstd, gamma, (float*)dz, (bf16_raw*)dx16, workspace, rows, drop_p, thr, bb_site_key(seed, offset),
                        bb_step_salt(), dz_dtype == BB_BF16 ? 1 : 0);
   });

@@ -47,16 +47,21 @@ __device__ __forceinline__ int cell_of(float ex, float ey, float ez, bool droppe
   return dim * (int)fz + (int)fx;
 }
 
+// LIFT_WAVES waves per sample.  With four (256 threads) a sample had one wave per SIMD of its CU -- 64 workgroups on 256
+// CUs -- and every phase below was a walk of P / 256 dependent steps per thread.  The result does not depend on the
+// number of waves (integer counts, and a placement whose order is that of the serial walk).
+#define LIFT_WAVES 16
+#define LIFT_THREADS (LIFT_WAVES * 64)
 template <int MODE>
-__global__ __launch_bounds__(256) void bev_bin_sort_kernel(LiftArgs a) {
+__global__ __launch_bounds__(LIFT_THREADS) void bev_bin_sort_kernel(LiftArgs a) {
   __shared__ short s_cell[MAX_POINTS];
   __shared__ int s_cnt[MAX_CELLS + 1];
   const int b = blockIdx.x, tid = threadIdx.x;
   const int K = a.dim * a.dim;
-  for (int c = tid; c <= K; c += 256) s_cnt[c] = 0;
+  for (int c = tid; c <= K; c += LIFT_THREADS) s_cnt[c] = 0;
   __syncthreads();
 
-  for (int p = tid; p < a.P; p += 256) {
+  for (int p = tid; p < a.P; p += LIFT_THREADS) {
     int cid;
     if (MODE == 0) {
       const int hw2 = a.hw * a.hw;
@@ -114,29 +119,29 @@ __global__ __launch_bounds__(256) void bev_bin_sort_kernel(LiftArgs a) {
     if (tid == 63) s_cnt[K] = incl;  // total kept points
   }
   __syncthreads();
-  for (int c = tid; c <= K; c += 256) a.cell_start[(size_t)b * (K + 1) + c] = s_cnt[c];
+  for (int c = tid; c <= K; c += LIFT_THREADS) a.cell_start[(size_t)b * (K + 1) + c] = s_cnt[c];
 
   // Stable placement (point ids ascending inside every cell), in parallel.  Round 2 let the thread that owns a cell
   // walk all P points (2 352 serial LDS reads per thread: 153 us for 64 workgroups, 1.5x the splat it feeds).  Now each
-  // of the four waves owns a contiguous quarter of the points: (A) per-wave cell counts, (B) per-cell exclusive prefix
-  // over the waves on top of the cell's start, (C) every wave walks its quarter 64 points at a time and ranks the lanes
+  // of the LIFT_WAVES waves owns a contiguous share of the points: (A) per-wave cell counts, (B) per-cell exclusive prefix
+  // over the waves on top of the cell's start, (C) every wave walks its share 64 points at a time and ranks the lanes
   // that share a cell with a compare mask (__ballot) -- lanes in ascending point order, waves in ascending ranges, so the
-  // order is exactly that of the serial walk.
-  __shared__ int s_wbase[4][MAX_CELLS + 1];
+  // order is exactly that of the serial walk.  LDS: 48 KB of cells + 4 KB of counts + 64 KB here, of gfx950's 160 KB.
+  __shared__ int s_wbase[LIFT_WAVES][MAX_CELLS + 1];
   const int lane = tid & 63, wv = tid >> 6;
-  for (int c = tid; c < 4 * (MAX_CELLS + 1); c += 256) (&s_wbase[0][0])[c] = 0;
+  for (int c = tid; c < LIFT_WAVES * (MAX_CELLS + 1); c += LIFT_THREADS) (&s_wbase[0][0])[c] = 0;
   __syncthreads();
-  const int per_wave = ((a.P + 255) / 256) * 64;              // points per wave, a multiple of 64
+  const int per_wave = ((a.P + LIFT_THREADS - 1) / LIFT_THREADS) * 64;   // points per wave, a multiple of 64
   const int pw0 = wv * per_wave;
   for (int p = pw0 + lane; p < pw0 + per_wave && p < a.P; p += 64) {
     const int cid = s_cell[p];
     if (cid >= 0) atomicAdd(&s_wbase[wv][cid], 1);
   }
   __syncthreads();
-  for (int c = tid; c < K; c += 256) {
+  for (int c = tid; c < K; c += LIFT_THREADS) {
     int base = s_cnt[c];
 #pragma unroll
-    for (int w = 0; w < 4; ++w) {
+    for (int w = 0; w < LIFT_WAVES; ++w) {
       const int n = s_wbase[w][c];
       s_wbase[w][c] = base;
       base += n;
@@ -253,7 +258,7 @@ BEVBERT_API int bevbert_bev_lift_bin(const float* depths, const float* T_c2w, co
   a.V = V; a.hw = hw; a.depth_scale = depth_scale; a.P = P; a.dim = dim; a.res = res;
   a.half = (float)(dim - 1) / 2.0f; a.y_clip = y_clip;
   a.cell = cell; a.order = order; a.cell_start = cell_start;
-  hipLaunchKernelGGL(bev_bin_sort_kernel<0>, dim3(B), dim3(256), 0, stream, a);
+  hipLaunchKernelGGL(bev_bin_sort_kernel<0>, dim3(B), dim3(LIFT_THREADS), 0, stream, a);
   BB_CHECK_LAUNCH("bev_lift_bin");
   return BB_OK;
 }
@@ -267,7 +272,7 @@ BEVBERT_API int bevbert_bev_bin_points(const float* points, const uint8_t* drop_
   a.points = points; a.pmask = drop_mask; a.P = P; a.dim = dim; a.res = res;
   a.half = (float)(dim - 1) / 2.0f; a.y_clip = y_clip;
   a.cell = cell; a.order = order; a.cell_start = cell_start;
-  hipLaunchKernelGGL(bev_bin_sort_kernel<1>, dim3(B), dim3(256), 0, stream, a);
+  hipLaunchKernelGGL(bev_bin_sort_kernel<1>, dim3(B), dim3(LIFT_THREADS), 0, stream, a);
   BB_CHECK_LAUNCH("bev_bin_points");
   return BB_OK;
 }
