@@ -557,6 +557,97 @@ int bevbert_wp_pano_inputs(const void* rgb_embeds, const void* depth_embeds, int
                            void* pano_rgb, void* pano_depth, void* rgb_fts, void* dep_fts, float* loc_fts,
                            int64_t* nav_types, int64_t* view_lens, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Ghost-node map of the continuous-environment agent (since 0.2.2; entry points added, ABI otherwise unchanged).
+ * Replaces bevbert_ce/vlnce_baselines/models/graph_utils.py:142-372 (GraphMap: identify_node, estimate_cand_pos,
+ * update_graph with its two networkx all-pairs Dijkstra runs, front_to_ghost_dist, get_pos_fts, get_neighbors) and
+ * ss_trainer_BEV.py:317-345 (_teacher_action_new from given distances), :465-475 (_discretize_polar_relpos), :477-532 (the
+ * candidate half of _nav_bev_variable), :534-611 (_nav_gmap_variable), :1083-1084 (stop scores), :1110-1179 (actions).
+ * B maps in dense arrays of fixed capacity: node k is the reference's str(k), ghost g its 'g' + str(g); ids in outputs
+ * are -1 = [stop] / none, k < N = node k, N + g = ghost g.  N <= 64, 1 + N + Gh <= 512.  No atomics, fixed output shapes,
+ * no entry synchronises with the host.  *overflow: 1 = a capacity (nodes, ghosts, positions per ghost, BEV candidates)
+ * was exceeded and the item was refused, 2 = an action that names no live ghost.  The reference's behaviours that are
+ * kept as they execute are listed in csrc/ce_map.hip.  Per-step host inputs: pose (B,4) f64 = x, y, z, heading;
+ * live (B) u8 (0: the map is left alone, its output rows are padding); step_id (1) i32 -- device memory, so a captured
+ * step replays with fresh values. */
+typedef struct bevbert_ce_state {
+  double* node_pos;   /* (B, N, 3) */
+  double* edge_w;     /* (B, N, N)  edge weights, < 0 = no edge */
+  double* dist;       /* (B, N, N)  shortest_dist[x][y], summed from x; +inf = none */
+  int* hops;          /* (B, N, N)  len(shortest_path[x][y]) (both end points), 0 = none */
+  int* pred;          /* (B, N, N)  predecessor of y on the path from x, -1 = none */
+  int* n_nodes;       /* (B) */
+  int* node_step;     /* (B, N) */
+  float* stop_score;  /* (B, N) */
+  void* node_embeds;  /* (B, N, H)  dtype */
+  int* g_cnt;         /* (B)  ghosts ever created: the next ghost id */
+  uint8_t* g_alive;   /* (B, Gh) */
+  int* g_npos;        /* (B, Gh)  observed positions = fronts = embedding count */
+  double* g_pos;      /* (B, Gh, P, 3) */
+  double* g_mean;     /* (B, Gh, 3) */
+  double* g_aug;      /* (B, Gh, 3)  mean + training noise */
+  float* g_sum;       /* (B, Gh, H)  embedding sums */
+  int* g_fronts;      /* (B, Gh, P) */
+  int* prev_vp;       /* (B)  -1 = none */
+  int* cur_vp;        /* (B)  node made by the last update */
+  uint8_t* merge;     /* (B)  merge_ghost of each map */
+  int* overflow;      /* (1) */
+  int B, N, Gh, P, H, dtype;
+} bevbert_ce_state;
+
+/* identify_node + estimate_cand_pos + update_graph of every live map: a new node at pose, the prev_vp edge, every
+ * candidate j < cand_count[b] (cand_angles / cand_distances (B,C) f32, C <= 16, as bevbert_wp_candidates writes them)
+ * localized to a node or created as / merged into a ghost with the j-th row of pano (B,L,H) whose nav_types (B,L) i64 is 1;
+ * avg_pano (B,H) becomes the node embedding (dtype of the state).  ghost_aug a > 0: every live ghost's augmented position
+ * is redrawn as mean + clip(N(0, (a, 0, a)), +-a), a pure function of (seed, step salt, step_id, b, ghost id).  Then
+ * all-pairs Dijkstra.  cand_slot (B,C): the id a candidate went to, -1 = padding / refused (a candidate
+ * without a nav_types == 1 row is refused with the overflow flag). */
+int bevbert_ce_update(const bevbert_ce_state* st, const double* pose, const uint8_t* live, const int* step_id,
+                      const int* cand_count, const float* cand_angles, const float* cand_distances, int C,
+                      const void* avg_pano, const void* pano, const int64_t* nav_types, int L, double loc_noise,
+                      double ghost_aug, uint32_t seed, int* cand_slot, hipStream_t stream);
+
+/* _nav_gmap_variable padded to G = 1 + N + Gh rows: [stop], the nodes in creation order, the live ghosts in creation
+ * order.  gmap_ids (B,G) i64, step_ids (B,G) i64, visited / masks (B,G) u8, img_fts (B,G,H) dtype (row 0 = 0, ghosts =
+ * sum / count), pos_fts (B,G,7) f32, pair_dists (B,G,G) f32, no_vp_left (B) u8. */
+int bevbert_ce_nav_vars(const bevbert_ce_state* st, const double* pose, const uint8_t* live, int64_t* gmap_ids,
+                        int64_t* step_ids, uint8_t* visited, uint8_t* masks, void* img_fts, float* pos_fts,
+                        float* pair_dists, uint8_t* no_vp_left, hipStream_t stream);
+
+/* get_neighbors + _discretize_polar_relpos: slot 0 = the current node (centre cell), the 1-hop nodes, the live ghosts
+ * with the current node among their fronts; at most K slots.  nav_masks (B,dim*dim) u8, cand_idxs / cand_ids (B,K) i64
+ * (padding 0 / -1), cand_n (B), gpos_fts (B,7) f32 = the start node's position features, and the SAP logit fusion's
+ * indices computed from the ids: src (B,G) i64 into [local (K) | backtrack | 0], vis_c (B,K) u8. */
+int bevbert_ce_bev_cands(const bevbert_ce_state* st, const double* pose, const uint8_t* live, int bev_dim, double bev_res,
+                         int K, uint8_t* nav_masks, int64_t* cand_idxs, int64_t* cand_ids, int* cand_n, float* gpos_fts,
+                         int64_t* src, uint8_t* vis_c, hipStream_t stream);
+
+/* node_stop_scores[cur_vp] = probs0[b * stride] for every live map. */
+int bevbert_ce_stop_scores(const bevbert_ce_state* st, const uint8_t* live, const float* probs0, int stride,
+                           hipStream_t stream);
+
+/* _teacher_action_new ('spl') from cur_dist (B) f64 and ghost_dist (B,Gh) f64 by ghost id: 0 when cur_dist < 1.5, -100
+ * when no ghost is left (and for maps that are not live), else the row of the first minimal live ghost.  out (B) i64. */
+int bevbert_ce_teacher(const bevbert_ce_state* st, const uint8_t* live, const double* cur_dist, const double* ghost_dist,
+                       int64_t* out, hipStream_t stream);
+
+/* ss_trainer_BEV.py:1110-1179 for a_t (B) i64 rows of gmap_ids (B,G): rec (B, 11 + 4 N) f64 = [act 0 / 4 (-1: not live or
+ * refused), cur, stop_vp / front_vp, ghost id (-1), len(back_path), back_path (N, -1 padded), stop / front position (3),
+ * ghost position (3), positions of back_path's nodes (N,3)]; sets prev_vp = front and, with consume_ghost, deletes the ghost. */
+int bevbert_ce_act(const bevbert_ce_state* st, const uint8_t* live, const int64_t* a_t, const int64_t* gmap_ids,
+                   int last_step, int consume_ghost, double* rec, hipStream_t stream);
+
+/* update_node_pc's store: for every live map, row b of src (B rows of row_bytes bytes, a multiple of 4) is copied into
+ * slot b * N + cur_vp[b] of store (B * N rows).  Called once each for the step's grid features, depths and camera matrices. */
+int bevbert_ce_remember(const bevbert_ce_state* st, const uint8_t* live, const void* src, void* store, int64_t row_bytes,
+                        hipStream_t stream);
+
+/* gather_node_pc(cur, order) as written: order 0 = the current node, else the nodes in creation order with
+ * len(shortest_path[cur][node]) <= order (both end points counted: order 1 is still the current node alone).  rows (B,R)
+ * store slots, row_live (B,R) u8; padding = the map's slot 0 with row_live 0; more than R nodes set *overflow. */
+int bevbert_ce_bev_select(const bevbert_ce_state* st, const uint8_t* live, int order, int R, int* rows, uint8_t* row_live,
+                          hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -68,7 +68,10 @@ class GlocalTextPathNavCMT(nn.Module):
     def forward_navigation_per_step(self, txt_embeds, txt_masks, gmap_img_embeds, gmap_step_ids, gmap_pos_fts,
                                     gmap_masks, gmap_pair_dists, gmap_visited_masks, gmap_vpids,
                                     bev_fts, bev_pos_fts, bev_masks, bev_nav_masks, bev_cand_idxs, bev_cand_vpids,
-                                    obj_embeds, obj_masks, gmap_visited_masks_host=None):
+                                    obj_embeds, obj_masks, gmap_visited_masks_host=None, sap_fusion=None):
+        """``sap_fusion`` = (src (B,G) int64, vis_c (B,K) bool) already on the device (ce_map.CEGraphMap.bev_inputs builds
+        them from integer ids): the host-side ``sap_fusion_indices`` over gmap_vpids / bev_cand_vpids is skipped and both
+        id lists may be None."""
         cd = txt_embeds.dtype
         g_in = self.global_encoder.pos_step_embedding(gmap_img_embeds.to(cd), gmap_step_ids, gmap_pos_fts)
         gmap_embeds = self.global_encoder(txt_embeds, txt_masks, g_in, gmap_masks, gmap_pair_dists)
@@ -89,12 +92,15 @@ class GlocalTextPathNavCMT(nn.Module):
         cand_masks = bev_nav_masks[bi, bev_cand_idxs]
         local_logits = self.local_sap_head(cand_embeds).squeeze(2).float() * (1 - fuse_weights)
         local_logits = local_logits.masked_fill(cand_masks.logical_not(), -float("inf"))
-        vis_host = gmap_visited_masks_host if gmap_visited_masks_host is not None else gmap_visited_masks.tolist()
-        src, vis_c = sap_fusion_indices(gmap_vpids, vis_host, bev_cand_vpids, gmap_embeds.shape[1],
-                                        bev_cand_idxs.shape[1])
-        dev = global_logits.device
-        fused_logits = fuse_sap_logits(global_logits, local_logits, torch.from_numpy(src).to(dev, non_blocking=True),
-                                       torch.from_numpy(vis_c).to(dev, non_blocking=True))
+        if sap_fusion is not None:
+            fused_logits = fuse_sap_logits(global_logits, local_logits, *sap_fusion)
+        else:
+            vis_host = gmap_visited_masks_host if gmap_visited_masks_host is not None else gmap_visited_masks.tolist()
+            src, vis_c = sap_fusion_indices(gmap_vpids, vis_host, bev_cand_vpids, gmap_embeds.shape[1],
+                                            bev_cand_idxs.shape[1])
+            dev = global_logits.device
+            fused_logits = fuse_sap_logits(global_logits, local_logits, torch.from_numpy(src).to(dev, non_blocking=True),
+                                           torch.from_numpy(vis_c).to(dev, non_blocking=True))
         obj_logits = None
         if obj_embeds is not None:                                      # map_nav_src/models/vilmodel.py:873-877
             obj_logits = self.og_head(obj_embeds).squeeze(2).float().masked_fill(obj_masks.logical_not(), -float("inf"))
@@ -115,7 +121,7 @@ class GlocalTextPathNavCMT(nn.Module):
                 batch["gmap_vpids"], batch["bev_fts"], batch["bev_pos_fts"], batch["bev_masks"],
                 batch["bev_nav_masks"], batch["bev_cand_idxs"], batch["bev_cand_vpids"],
                 batch.get("obj_embeds"), batch.get("obj_masks"),
-                gmap_visited_masks_host=batch.get("gmap_visited_masks_cpu"))
+                gmap_visited_masks_host=batch.get("gmap_visited_masks_cpu"), sap_fusion=batch.get("sap_fusion"))
         raise NotImplementedError("wrong mode: %s" % mode)
 
 
