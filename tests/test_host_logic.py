@@ -168,6 +168,89 @@ def test_layernorm_width_and_dtype_dispatch_answers_without_a_gpu():
             assert rc == -3 and b"dtype 2 unsupported" in l.bevbert_last_error(), (name, H, rc, l.bevbert_last_error())
 
 
+def _dtype_answer_rows(l):
+    """(entry, call(dtype), return code, message) for every launcher that picks a kernel instantiation from a runtime dtype."""
+    N = None
+    buf = (ctypes.c_uint8 * 64)()
+    p = ctypes.addressof(buf)          # non-null wherever an entry checks a pointer before it looks at the dtype
+    from vln_bevbert_amd.graph_map_dev import _GmState
+    gm = _GmState(pos=p, dis=p, point=p, hops=p, visited=p, step_ids=p, B=1, N=1, V=1)
+    gm.keep = buf                      # the rows' closures hold gm, gm holds the buffer its pointers name
+    st = ctypes.byref(gm)
+    strides = (ctypes.c_int64 * 8)(*([64] * 8))
+    unsup, inval = -3, -1
+    return [
+        # rowops.hip
+        ("colsum_any", lambda dt: l.bevbert_colsum_any(N, N, 1, 4, dt, 0, N), unsup, "colsum_any: dtype %d unsupported"),
+        ("bce_rows_fwd", lambda dt: l.bevbert_bce_rows_fwd(N, N, N, N, 1, 4, dt, N), unsup, "bce_rows_fwd: dtype %d unsupported"),
+        ("bce_rows_bwd", lambda dt: l.bevbert_bce_rows_bwd(N, N, N, N, N, 1, 4, dt, N), unsup, "bce_rows_bwd: dtype %d unsupported"),
+        ("bias_gelu_fwd", lambda dt: l.bevbert_bias_gelu_fwd(N, N, N, 1, 4, dt, N), unsup, "bias_act_fwd: dtype %d unsupported"),
+        ("bias_gelu_fwd C=8", lambda dt: l.bevbert_bias_gelu_fwd(N, N, N, 1, 8, dt, N), unsup, "bias_act_fwd: dtype %d unsupported"),
+        ("bias_relu_fwd", lambda dt: l.bevbert_bias_relu_fwd(N, N, N, 1, 4, dt, N), unsup, "bias_act_fwd: dtype %d unsupported"),
+        ("bias_gelu_bwd", lambda dt: l.bevbert_bias_gelu_bwd(N, N, N, N, N, N, 1, 4, dt, 0, N), unsup, "bias_act_bwd: dtype %d unsupported"),
+        ("bias_relu_bwd", lambda dt: l.bevbert_bias_relu_bwd(N, N, N, N, N, N, 1, 4, dt, 0, N), unsup, "bias_act_bwd: dtype %d unsupported"),
+        ("colsum", lambda dt: l.bevbert_colsum(N, N, N, 1, 4, dt, 0, N), unsup, "colsum: dtype %d unsupported"),
+        ("colsum_partials", lambda dt: l.bevbert_colsum_partials(N, N, 1, 4, dt, N), unsup, "colsum_partials: dtype %d unsupported"),
+        ("segment_wsum", lambda dt: l.bevbert_segment_wsum(N, N, N, N, N, 1, 4, dt, N), unsup, "segment_wsum: dtype %d unsupported"),
+        ("accum_partials", lambda dt: l.bevbert_accum_partials(N, N, 1, 4, dt, N), unsup, "accum_partials: dtype %d unsupported"),
+        ("rows_gather", lambda dt: l.bevbert_rows_gather(N, N, N, 1, 4, dt, N), unsup, "rows_gather: dtype %d unsupported"),
+        ("rows_scatter", lambda dt: l.bevbert_rows_scatter(N, N, N, 1, 4, dt, 0, N), unsup, "rows_scatter: dtype %d unsupported"),
+        ("rows_scatter +=", lambda dt: l.bevbert_rows_scatter(N, N, N, 1, 4, dt, 1, N), unsup, "rows_scatter: dtype %d unsupported"),
+        ("embedding_grad", lambda dt: l.bevbert_embedding_grad(N, N, N, 1, 4, 0, dt, N), unsup, "embedding_grad: dtype %d unsupported"),
+        ("embedding_grad_sliced", lambda dt: l.bevbert_embedding_grad_sliced(N, N, N, 1, 4, 1, 1, dt, N), unsup,
+         "embedding_grad_sliced: dtype %d unsupported"),
+        ("cast_f32", lambda dt: l.bevbert_cast_f32(N, N, 4, dt, N), unsup, "cast_f32: dst dtype %d unsupported"),
+        # smallk.hip
+        ("smallk_fwd", lambda dt: l.bevbert_smallk_linear_layernorm_fwd(*[N] * 11, 1, 1, 256, 1e-12, dt, N), unsup,
+         "smallk_linear_layernorm_fwd: dtype %d unsupported"),
+        ("smallk_bwd", lambda dt: l.bevbert_smallk_linear_layernorm_bwd(N, N, N, N, gm.pos, gm.pos, N, N, N, N, N, gm.pos, 1, 1, 256, dt, N), unsup,
+         "smallk_linear_layernorm_bwd: dtype %d unsupported"),
+        # sap_loss.hip
+        ("sap_loss_fwd", lambda dt: l.bevbert_sap_loss_fwd(*[N] * 15, 1, 1, 1, 1, dt, N), unsup, "sap_loss: dtype %d unsupported"),
+        ("sap_loss_bwd", lambda dt: l.bevbert_sap_loss_bwd(*[N] * 7, 1, 1, 1, dt, N), unsup, "sap_loss: dtype %d unsupported"),
+        ("cross_entropy_fwd", lambda dt: l.bevbert_cross_entropy_fwd(N, N, N, N, 1, 4, dt, N), unsup, "cross_entropy: dtype %d unsupported"),
+        ("cross_entropy_bwd", lambda dt: l.bevbert_cross_entropy_bwd(N, N, N, N, N, 1, 4, dt, N), unsup, "cross_entropy: dtype %d unsupported"),
+        # nav_expert.hip
+        ("nav_ce_fwd", lambda dt: l.bevbert_nav_ce_fwd(N, N, N, 1, 4, -100, dt, N), unsup, "nav_ce: dtype %d unsupported"),
+        ("nav_ce_bwd", lambda dt: l.bevbert_nav_ce_bwd(N, N, N, N, N, 1, 4, -100, dt, N), unsup, "nav_ce: dtype %d unsupported"),
+        # graph_nav.hip (a host-side state struct passes gm_check before the dtype is looked at)
+        ("gm_embed_update", lambda dt: l.bevbert_gm_embed_update(st, *[N] * 8, 1, 1, 4, dt, N), unsup, "gm_embed_update: dtype %d unsupported"),
+        ("gm_node_embeds", lambda dt: l.bevbert_gm_node_embeds(st, N, N, N, N, 1, 4, dt, N, N), unsup, "gm_node_embeds: dtype %d unsupported"),
+        # waypoint.hip: the dtype is an argument check like the others there
+        ("wp_ring_attn", lambda dt: l.bevbert_wp_ring_attn(N, N, 1, 1, 1.0, dt, N), inval, "wp_ring_attn: dtype %d unsupported"),
+        ("wp_pano_inputs", lambda dt: l.bevbert_wp_pano_inputs(N, N, dt, 1, *[N] * 12), inval, "wp_pano_inputs: dtype %d unsupported"),
+        # attn_simple.hip: its three launchers sit behind the dtype check of the two attention entries
+        ("attn_fwd", lambda dt: l.bevbert_attn_fwd(N, N, N, N, N, N, N, strides, 1, 1, 4, 4, 64, 0.125, dt, 1, 0.0, 0, 0, N, 0, N), inval,
+         "attn_fwd: dtype %d unsupported"),
+        ("attn_bwd", lambda dt: l.bevbert_attn_bwd(*[N] * 13, strides, 1, 1, 4, 4, 64, 0.125, dt, 1, 0.0, 0, 0, N, N), inval,
+         "attn_bwd: dtype %d unsupported"),
+    ]
+
+
+def test_every_dtype_dispatching_entry_answers_a_dtype_without_a_kernel_before_any_launch():
+    """One row per launcher that turns a runtime dtype into a kernel instantiation: the smallest arguments that pass its
+    shape checks (null pointers, one row), a dtype code it has no kernel for, and what it answers -- the code and the
+    message, recorded from the library before these launchers shared one dispatch helper.  fp16 (2) is unknown to all of
+    them but cast_f32, which converts to bf16 or fp16 and refuses fp32 (0) and 3."""
+    l = lib.load()
+    for name, call, want_rc, want_msg in _dtype_answer_rows(l):
+        for dt in ((0, 3) if name == "cast_f32" else (2, 3, -1)):
+            rc = call(dt)
+            msg = l.bevbert_last_error().decode()
+            assert rc == want_rc and want_msg % dt in msg, (name, dt, rc, msg)
+    # the small-K entries refuse a width they have no kernel for before they look at the dtype
+    buf = (ctypes.c_uint8 * 64)()
+    N, p = None, ctypes.addressof(buf)
+    for H in (100, 1280):
+        rc = l.bevbert_smallk_linear_layernorm_fwd(*[N] * 11, 1, 1, H, 1e-12, 2, N)
+        assert rc == -1 and f"smallk_linear_layernorm_fwd: H={H} unsupported" in l.bevbert_last_error().decode()
+        rc = l.bevbert_smallk_linear_layernorm_bwd(N, N, N, N, p, p, N, N, N, N, N, p, 1, 1, H, 2, N)
+        assert rc == -1 and f"smallk_linear_layernorm_bwd: H={H} unsupported" in l.bevbert_last_error().decode()
+    # and every entry returns before its dtype check when there are no rows
+    assert l.bevbert_colsum(N, N, N, 0, 4, 2, 0, N) == 0 and l.bevbert_rows_scatter(N, N, N, 0, 4, 2, 0, N) == 0
+    assert l.bevbert_sap_loss_fwd(*[N] * 15, 0, 1, 1, 1, 2, N) == 0 and l.bevbert_nav_ce_bwd(N, N, N, N, N, 0, 4, -100, 2, N) == 0
+
+
 def test_cpu_tensors_fail_loudly():
     from vln_bevbert_amd import ops
     with pytest.raises(lib.BevBertHipError):

@@ -145,19 +145,18 @@ __global__ __launch_bounds__(256) void attn_simple_dkv_kernel(AttnArgs a) {
   io<T>::st((T*)a.dv + (size_t)b * a.bsv + (size_t)key * a.ldv + h * ATTN_D + lane, dv);
 }
 
+// dtype: fp32 or bf16, checked by the attention entries (capi.hip) before they come here
 int attn_simple_fwd(const AttnArgs& a, int dtype, hipStream_t st) {
   BB_REQUIRE(a.Lk <= LK_MAX, "attention (exact path): Lk=%d exceeds %d", a.Lk, LK_MAX);
   const dim3 grid((a.Lq + 3) / 4, a.nh, a.B);
-  if (dtype == BB_F32) hipLaunchKernelGGL(attn_simple_fwd_kernel<float>, grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(attn_simple_fwd_kernel<bf16_raw>, grid, dim3(256), 0, st, a);
+  bb_with_type(dtype, [&](auto t) { hipLaunchKernelGGL(attn_simple_fwd_kernel<decltype(t)>, grid, dim3(256), 0, st, a); });
   BB_CHECK_LAUNCH("attn_fwd(exact)");
   return BB_OK;
 }
 
 int attn_delta(const AttnArgs& a, float* delta, int dtype, hipStream_t st) {
   const dim3 grid((a.Lq + 3) / 4, a.nh, a.B);
-  if (dtype == BB_F32) hipLaunchKernelGGL(attn_delta_kernel<float>, grid, dim3(256), 0, st, a, delta);
-  else hipLaunchKernelGGL(attn_delta_kernel<bf16_raw>, grid, dim3(256), 0, st, a, delta);
+  bb_with_type(dtype, [&](auto t) { hipLaunchKernelGGL(attn_delta_kernel<decltype(t)>, grid, dim3(256), 0, st, a, delta); });
   BB_CHECK_LAUNCH("attn_delta");
   return BB_OK;
 }
@@ -165,13 +164,10 @@ int attn_delta(const AttnArgs& a, float* delta, int dtype, hipStream_t st) {
 int attn_simple_bwd(const AttnArgs& a, int dtype, hipStream_t st) {
   BB_REQUIRE(a.Lk <= LK_MAX, "attention (exact path): Lk=%d exceeds %d", a.Lk, LK_MAX);
   const dim3 gq((a.Lq + 3) / 4, a.nh, a.B), gk((a.Lk + 3) / 4, a.nh, a.B);
-  if (dtype == BB_F32) {
-    hipLaunchKernelGGL(attn_simple_dq_kernel<float>, gq, dim3(256), 0, st, a);
-    hipLaunchKernelGGL(attn_simple_dkv_kernel<float>, gk, dim3(256), 0, st, a);
-  } else {
-    hipLaunchKernelGGL(attn_simple_dq_kernel<bf16_raw>, gq, dim3(256), 0, st, a);
-    hipLaunchKernelGGL(attn_simple_dkv_kernel<bf16_raw>, gk, dim3(256), 0, st, a);
-  }
+  bb_with_type(dtype, [&](auto t) {
+    hipLaunchKernelGGL(attn_simple_dq_kernel<decltype(t)>, gq, dim3(256), 0, st, a);
+    hipLaunchKernelGGL(attn_simple_dkv_kernel<decltype(t)>, gk, dim3(256), 0, st, a);
+  });
   BB_CHECK_LAUNCH("attn_bwd(exact)");
   return BB_OK;
 }

@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <type_traits>
 
 #define BEVBERT_API extern "C" __attribute__((visibility("default")))
 
@@ -34,6 +35,38 @@ void bb_set_error(const char* fmt, ...);
   } while (0)
 
 typedef unsigned short bf16_raw;
+
+// ---- host: a runtime dtype / width / flag becomes a template argument -----------------------
+// The launchers of the C ABI write their launch line ONCE, in a generic lambda that receives the storage type (T{}), the
+// width or the flag (std::integral_constant) as a value; the helpers call it for the matching case and say whether
+// there was one (f is not called otherwise).  The cases are tried in the order given either way; the compiler
+// instantiates a left fold from its first case and a right fold from its last, and that is the order in which the
+// kernels land in the code object -- bb_with_width stays the right fold the LayerNorm entries were compiled with.
+template <typename T> struct bb_dtype_of;
+template <> struct bb_dtype_of<float> : std::integral_constant<int, BB_F32> {};
+template <> struct bb_dtype_of<bf16_raw> : std::integral_constant<int, BB_BF16> {};
+template <> struct bb_dtype_of<_Float16> : std::integral_constant<int, BB_F16> {};
+template <typename... Ts, typename F>
+static bool bb_with_type_of(int dtype, F&& f) {      // the storage type among Ts... whose code is `dtype`
+  return (... || (dtype == bb_dtype_of<Ts>::value ? (f(Ts{}), true) : false));
+}
+template <typename F>
+static bool bb_with_type(int dtype, F&& f) { return bb_with_type_of<float, bf16_raw>(dtype, f); }
+template <int... Ns, typename F>
+static bool bb_with_width(int H, F&& f) {            // NV = H / 256 when it is one of Ns...
+  return ((H / 256 == Ns ? (f(std::integral_constant<int, Ns>{}), true) : false) || ...);
+}
+template <int... Vs, typename F>
+static bool bb_with_int(int v, F&& f) {              // a small runtime int (an activation, a mode) among Vs...
+  return (... || (v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false));
+}
+template <typename F>
+static void bb_with_bool(bool b, F&& f) { b ? f(std::true_type{}) : f(std::false_type{}); }
+// the tail of an entry whose dtype has no kernel
+inline int bb_dtype_unsupported(const char* name, int dtype) {
+  bb_set_error("%s: dtype %d unsupported", name, dtype);
+  return BB_EUNSUPPORTED;
+}
 
 // ---- scalar conversions (round-to-nearest-even, NaN preserved) ----------------------------
 __device__ __forceinline__ float bf16_to_f32(bf16_raw v) { return __uint_as_float(((uint32_t)v) << 16); }

@@ -356,16 +356,12 @@ BEVBERT_API int bevbert_gm_embed_update(const GmState* st, void* embed_sum, floa
   if (int rc = gm_check(st, "gm_embed_update")) return rc;
   BB_REQUIRE(H % 4 == 0 && C >= 1 && V >= 1, "gm_embed_update: H=%d C=%d V=%d", H, C, V);
   const dim3 grid(st->B, 1 + C);
-  if (dtype == BB_F32)
-    hipLaunchKernelGGL(gm_embed_update_kernel<float>, grid, dim3(256), 0, stream, *st, (float*)embed_sum, embed_cnt,
-                       (const float*)avg, (const float*)pano, live, cur, ncand, cand, C, V, H);
-  else if (dtype == BB_BF16)
-    hipLaunchKernelGGL(gm_embed_update_kernel<bf16_raw>, grid, dim3(256), 0, stream, *st, (bf16_raw*)embed_sum, embed_cnt,
-                       (const bf16_raw*)avg, (const bf16_raw*)pano, live, cur, ncand, cand, C, V, H);
-  else {
-    bb_set_error("gm_embed_update: dtype %d unsupported", dtype);
-    return BB_EUNSUPPORTED;
-  }
+  const bool type_ok = bb_with_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(gm_embed_update_kernel<T>, grid, dim3(256), 0, stream, *st, (T*)embed_sum, embed_cnt, (const T*)avg,
+                       (const T*)pano, live, cur, ncand, cand, C, V, H);
+  });
+  if (!type_ok) return bb_dtype_unsupported("gm_embed_update", dtype);
   BB_CHECK_LAUNCH("gm_embed_update");
   return BB_OK;
 }
@@ -375,16 +371,12 @@ BEVBERT_API int bevbert_gm_node_embeds(const GmState* st, const void* embed_sum,
   if (int rc = gm_check(st, "gm_node_embeds")) return rc;
   BB_REQUIRE(H % 4 == 0 && G >= 1, "gm_node_embeds: H=%d G=%d", H, G);
   const dim3 grid(st->B, G);
-  if (dtype == BB_F32)
-    hipLaunchKernelGGL(gm_node_embeds_kernel<float>, grid, dim3(256), 0, stream, *st, (const float*)embed_sum, embed_cnt, node,
-                       cnt, G, H, (float*)out);
-  else if (dtype == BB_BF16)
-    hipLaunchKernelGGL(gm_node_embeds_kernel<bf16_raw>, grid, dim3(256), 0, stream, *st, (const bf16_raw*)embed_sum, embed_cnt,
-                       node, cnt, G, H, (bf16_raw*)out);
-  else {
-    bb_set_error("gm_node_embeds: dtype %d unsupported", dtype);
-    return BB_EUNSUPPORTED;
-  }
+  const bool type_ok = bb_with_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(gm_node_embeds_kernel<T>, grid, dim3(256), 0, stream, *st, (const T*)embed_sum, embed_cnt, node, cnt, G, H,
+                       (T*)out);
+  });
+  if (!type_ok) return bb_dtype_unsupported("gm_node_embeds", dtype);
   BB_CHECK_LAUNCH("gm_node_embeds");
   return BB_OK;
 }

@@ -372,16 +372,11 @@ __global__ __launch_bounds__(64) void ne_ce_bwd_kernel(const T* __restrict__ x, 
 BEVBERT_API int bevbert_nav_ce_fwd(const void* logits, const int64_t* target, float* out, int B, int C, int ignore,
                                    int dtype, hipStream_t stream) {
   BB_REQUIRE(C >= 1 && B >= 0, "nav_ce: B=%d C=%d", B, C);
-  if (dtype == BB_F32)
-    hipLaunchKernelGGL(ne_ce_fwd_kernel<float>, dim3(1), dim3(256), 0, stream, (const float*)logits, target, out, B, C,
-                       ignore);
-  else if (dtype == BB_BF16)
-    hipLaunchKernelGGL(ne_ce_fwd_kernel<bf16_raw>, dim3(1), dim3(256), 0, stream, (const bf16_raw*)logits, target, out, B,
-                       C, ignore);
-  else {
-    bb_set_error("nav_ce: dtype %d unsupported", dtype);
-    return BB_EUNSUPPORTED;
-  }
+  const bool type_ok = bb_with_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(ne_ce_fwd_kernel<T>, dim3(1), dim3(256), 0, stream, (const T*)logits, target, out, B, C, ignore);
+  });
+  if (!type_ok) return bb_dtype_unsupported("nav_ce", dtype);
   BB_CHECK_LAUNCH("nav_ce_fwd");
   return BB_OK;
 }
@@ -390,16 +385,12 @@ BEVBERT_API int bevbert_nav_ce_bwd(const void* logits, const int64_t* target, co
                                    void* dlogits, int B, int C, int ignore, int dtype, hipStream_t stream) {
   BB_REQUIRE(C >= 1, "nav_ce: C=%d", C);
   if (B <= 0) return BB_OK;
-  if (dtype == BB_F32)
-    hipLaunchKernelGGL(ne_ce_bwd_kernel<float>, dim3(B), dim3(64), 0, stream, (const float*)logits, target, out, dloss,
-                       (float*)dlogits, C, ignore);
-  else if (dtype == BB_BF16)
-    hipLaunchKernelGGL(ne_ce_bwd_kernel<bf16_raw>, dim3(B), dim3(64), 0, stream, (const bf16_raw*)logits, target, out,
-                       dloss, (bf16_raw*)dlogits, C, ignore);
-  else {
-    bb_set_error("nav_ce: dtype %d unsupported", dtype);
-    return BB_EUNSUPPORTED;
-  }
+  const bool type_ok = bb_with_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(ne_ce_bwd_kernel<T>, dim3(B), dim3(64), 0, stream, (const T*)logits, target, out, dloss, (T*)dlogits, C,
+                       ignore);
+  });
+  if (!type_ok) return bb_dtype_unsupported("nav_ce", dtype);
   BB_CHECK_LAUNCH("nav_ce_bwd");
   return BB_OK;
 }

@@ -1065,14 +1065,11 @@ BEVBERT_API int bevbert_colsum_any(const void* dy, float* out, int rows, int C, 
   BB_REQUIRE(rows >= 0 && C > 0, "colsum_any: rows=%d C=%d", rows, C);
   if (rows == 0) return BB_OK;
   const dim3 grid(C <= 4 ? 1 : (C + 63) / 64);
-  if (dtype == BB_F32)
-    hipLaunchKernelGGL(colsum_any_kernel<float>, grid, dim3(256), 0, stream, (const float*)dy, out, rows, C, accumulate);
-  else if (dtype == BB_BF16)
-    hipLaunchKernelGGL(colsum_any_kernel<bf16_raw>, grid, dim3(256), 0, stream, (const bf16_raw*)dy, out, rows, C, accumulate);
-  else {
-    bb_set_error("colsum_any: dtype %d unsupported", dtype);
-    return BB_EUNSUPPORTED;
-  }
+  const bool type_ok = bb_with_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(colsum_any_kernel<T>, grid, dim3(256), 0, stream, (const T*)dy, out, rows, C, accumulate);
+  });
+  if (!type_ok) return bb_dtype_unsupported("colsum_any", dtype);
   BB_CHECK_LAUNCH("colsum_any");
   return BB_OK;
 }
@@ -1197,9 +1194,11 @@ BEVBERT_API int bevbert_bce_rows_fwd(const void* logits, const uint8_t* labels, 
   BB_REQUIRE(rows >= 0 && C > 0, "bce_rows_fwd: rows=%d C=%d", rows, C);
   if (rows == 0) return BB_OK;
   const dim3 grid((rows + 3) / 4);
-  if (dtype == BB_F32) hipLaunchKernelGGL(bce_rows_fwd_kernel<float>, grid, dim3(256), 0, stream, (const float*)logits, labels, idx, out, rows, C);
-  else if (dtype == BB_BF16) hipLaunchKernelGGL(bce_rows_fwd_kernel<bf16_raw>, grid, dim3(256), 0, stream, (const bf16_raw*)logits, labels, idx, out, rows, C);
-  else { bb_set_error("bce_rows_fwd: dtype %d unsupported", dtype); return BB_EUNSUPPORTED; }
+  const bool type_ok = bb_with_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(bce_rows_fwd_kernel<T>, grid, dim3(256), 0, stream, (const T*)logits, labels, idx, out, rows, C);
+  });
+  if (!type_ok) return bb_dtype_unsupported("bce_rows_fwd", dtype);
   BB_CHECK_LAUNCH("bce_rows_fwd");
   return BB_OK;
 }
@@ -1209,9 +1208,11 @@ BEVBERT_API int bevbert_bce_rows_bwd(const void* logits, const uint8_t* labels, 
   BB_REQUIRE(rows >= 0 && C > 0, "bce_rows_bwd: rows=%d C=%d", rows, C);
   if (rows == 0) return BB_OK;
   const dim3 grid((rows + 3) / 4);
-  if (dtype == BB_F32) hipLaunchKernelGGL(bce_rows_bwd_kernel<float>, grid, dim3(256), 0, stream, (const float*)logits, labels, idx, g, (float*)dlogits, rows, C);
-  else if (dtype == BB_BF16) hipLaunchKernelGGL(bce_rows_bwd_kernel<bf16_raw>, grid, dim3(256), 0, stream, (const bf16_raw*)logits, labels, idx, g, (bf16_raw*)dlogits, rows, C);
-  else { bb_set_error("bce_rows_bwd: dtype %d unsupported", dtype); return BB_EUNSUPPORTED; }
+  const bool type_ok = bb_with_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(bce_rows_bwd_kernel<T>, grid, dim3(256), 0, stream, (const T*)logits, labels, idx, g, (T*)dlogits, rows, C);
+  });
+  if (!type_ok) return bb_dtype_unsupported("bce_rows_bwd", dtype);
   BB_CHECK_LAUNCH("bce_rows_bwd");
   return BB_OK;
 }
@@ -1288,20 +1289,6 @@ BEVBERT_API int bevbert_graph_bias_bwd(const float* dbias, const float* dists, i
 // =============================================================================================
 // C ABI
 // =============================================================================================
-// Compile-time selection for the LayerNorm entries: f(T{}) with the activation type of `dtype`, f(integral_constant<NV>)
-// with NV = H / 256 when it is one of Ns...; false when there is no such type / width (f is not called).
-template <typename F>
-static bool with_act_type(int dtype, F&& f) {
-  if (dtype == BB_F32) f(float{});
-  else if (dtype == BB_BF16) f(bf16_raw{});
-  else return false;
-  return true;
-}
-template <int... Ns, typename F>
-static bool with_width(int H, F&& f) {
-  return ((H / 256 == Ns ? (f(std::integral_constant<int, Ns>{}), true) : false) || ...);
-}
-
 // the three plain forward entries behind their argument checks; `name` as in their messages
 template <bool GATHER>
 static int ln_fwd_launch(const char* name, hipStream_t st, const void* x, const float* bias, const void* residual,
@@ -1311,18 +1298,15 @@ static int ln_fwd_launch(const char* name, hipStream_t st, const void* x, const 
   const dim3 grid((rows + 3) / 4);
   const uint32_t thr = bb_drop_threshold(p);
   bool width_ok = false;
-  const bool type_ok = with_act_type(dtype, [&](auto t) {
+  const bool type_ok = bb_with_type(dtype, [&](auto t) {
     using T = decltype(t);
-    width_ok = with_width<1, 2, 3, 4, 6, 8>(H, [&](auto nv) {
+    width_ok = bb_with_width<1, 2, 3, 4, 6, 8>(H, [&](auto nv) {
       hipLaunchKernelGGL((ln_fwd_kernel<T, decltype(nv)::value, GATHER>), grid, dim3(256), 0, st, (const T*)x, bias, (const T*)residual,
                          gamma, beta, (T*)y, (T*)z_out, mean, rstd, rows, eps, p, thr, bb_site_key(seed, offset), ids,
                          (const T*)word, (const T*)pos, (const T*)type_row, L, bb_step_salt());
     });
   });
-  if (!type_ok) {
-    bb_set_error("%s: dtype %d unsupported", name, dtype);
-    return BB_EUNSUPPORTED;
-  }
+  if (!type_ok) return bb_dtype_unsupported(name, dtype);
   if (!width_ok) {
     bb_set_error("layernorm: H=%d unsupported (need H in {256,512,768,1024,1536,2048})", H);
     return BB_EUNSUPPORTED;
@@ -1423,18 +1407,15 @@ static int layernorm_bwd_impl(const void* dy, const void* z, const float* mean, 
   const int nb = colwise_blocks(rows);
   const uint32_t thr = bb_drop_threshold(drop_p);
   bool width_ok = false;
-  const bool type_ok = with_act_type(dtype, [&](auto t) {
+  const bool type_ok = bb_with_type(dtype, [&](auto t) {
     using T = decltype(t);
-    width_ok = with_width<1, 2, 3, 4>(H, [&](auto nv) {
+    width_ok = bb_with_width<1, 2, 3, 4>(H, [&](auto nv) {
       hipLaunchKernelGGL((ln_bwd_kernel<T, decltype(nv)::value>), dim3(nb), dim3(256), 0, stream, (const T*)dy, (const T*)z, mean, rstd,
                          gamma, (T*)dz, (T*)dx, workspace, rows, drop_p, thr, bb_site_key(seed, offset), bb_step_salt(),
                          (const T*)dz_add);
     });
   });
-  if (!type_ok) {
-    bb_set_error("layernorm_bwd: dtype %d unsupported", dtype);
-    return BB_EUNSUPPORTED;
-  }
+  if (!type_ok) return bb_dtype_unsupported("layernorm_bwd", dtype);
   if (!width_ok) {
     bb_set_error("layernorm_bwd: H=%d unsupported", H);
     return BB_EUNSUPPORTED;
@@ -1477,9 +1458,9 @@ BEVBERT_API int bevbert_layernorm_res32_fwd(const void* x, const float* bias, co
   if (rows == 0) return BB_OK;
   const dim3 grid((rows + 3) / 4);
   const uint32_t thr = bb_drop_threshold(drop_p);
-  with_act_type(residual != nullptr && residual_dtype == BB_BF16 ? BB_BF16 : BB_F32, [&](auto t) {
+  bb_with_type(residual != nullptr && residual_dtype == BB_BF16 ? BB_BF16 : BB_F32, [&](auto t) {
     using TR = decltype(t);
-    with_width<1, 2, 3, 4>(H, [&](auto nv) {
+    bb_with_width<1, 2, 3, 4>(H, [&](auto nv) {
       hipLaunchKernelGGL((ln_res32_fwd_kernel<TR, decltype(nv)::value>), grid, dim3(256), 0, stream, (const bf16_raw*)x, bias,
                          (const TR*)residual, gamma, beta, (bf16_raw*)y16, y32, z32, mean, rstd, rows, eps, drop_p, thr,
                          bb_site_key(seed, offset), bb_step_salt());
@@ -1500,7 +1481,7 @@ BEVBERT_API int bevbert_layernorm_res32_bwd(const void* dy16, const float* dy32,
   if (rows <= 0) return BB_OK;
   const int nb = colwise_blocks(rows);
   const uint32_t thr = bb_drop_threshold(drop_p);
-  with_width<1, 2, 3, 4>(H, [&](auto nv) {
+  bb_with_width<1, 2, 3, 4>(H, [&](auto nv) {
     auto* kernel = ln_res32_bwd_loads_ahead(nb) ? ln_res32_bwd_ahead_kernel<decltype(nv)::value> : ln_res32_bwd_kernel<decltype(nv)::value>;
     hipLaunchKernelGGL(kernel, dim3(nb), dim3(256), 0, stream, (const bf16_raw*)dy16, dy32, z32, mean,
                        rstd, gamma, (float*)dz, (bf16_raw*)dx16, workspace, rows, drop_p, thr, bb_site_key(seed, offset),
@@ -1517,19 +1498,16 @@ static int bias_act_fwd(const void* x, const float* bias, void* y, int rows, int
   BB_REQUIRE(act == 0 || act == 1, "bias_act_fwd: activation %d (0 erf-GELU, 1 ReLU)", act);
   if (rows <= 0) return BB_OK;
   const dim3 grid(elementwise_row_groups(rows), (C + 1023) / 1024);
-  if (dtype == BB_F32 && act == 0)
-    hipLaunchKernelGGL((bias_gelu_fwd_kernel<float, 0>), grid, dim3(256), 0, stream, (const float*)x, bias, (float*)y, rows, C);
-  else if (dtype == BB_F32)
-    hipLaunchKernelGGL((bias_gelu_fwd_kernel<float, 1>), grid, dim3(256), 0, stream, (const float*)x, bias, (float*)y, rows, C);
-  else if (dtype == BB_BF16 && act == 0 && C % 8 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0)   // 71 vs 76 us at 28224 x 3072
+  if (dtype == BB_BF16 && act == 0 && C % 8 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0) {   // 71 vs 76 us at 28224 x 3072
     hipLaunchKernelGGL(bias_gelu_fwd8_kernel, grid, dim3(128), 0, stream, (const bf16_raw*)x, bias, (bf16_raw*)y, rows, C);
-  else if (dtype == BB_BF16 && act == 0)
-    hipLaunchKernelGGL((bias_gelu_fwd_kernel<bf16_raw, 0>), grid, dim3(256), 0, stream, (const bf16_raw*)x, bias, (bf16_raw*)y, rows, C);
-  else if (dtype == BB_BF16)
-    hipLaunchKernelGGL((bias_gelu_fwd_kernel<bf16_raw, 1>), grid, dim3(256), 0, stream, (const bf16_raw*)x, bias, (bf16_raw*)y, rows, C);
-  else {
-    bb_set_error("bias_act_fwd: dtype %d unsupported", dtype);
-    return BB_EUNSUPPORTED;
+  } else {
+    const bool type_ok = bb_with_type(dtype, [&](auto t) {
+      using T = decltype(t);
+      bb_with_int<0, 1>(act, [&](auto a) {
+        hipLaunchKernelGGL((bias_gelu_fwd_kernel<T, decltype(a)::value>), grid, dim3(256), 0, stream, (const T*)x, bias, (T*)y, rows, C);
+      });
+    });
+    if (!type_ok) return bb_dtype_unsupported("bias_act_fwd", dtype);
   }
   BB_CHECK_LAUNCH("bias_act_fwd");
   return BB_OK;
@@ -1542,18 +1520,14 @@ static int bias_act_bwd(const void* dy, const void* x, const float* bias, void* 
   if (rows <= 0) return BB_OK;
   const int nb = colwise_blocks(rows);
   const dim3 grid(nb, (C + 1023) / 1024);
-  if (dtype == BB_F32 && act == 0)
-    hipLaunchKernelGGL((colwise_bwd_kernel<float, 0>), grid, dim3(256), 0, stream, (const float*)dy, (const float*)x, bias, (float*)dx, workspace, rows, C);
-  else if (dtype == BB_F32)
-    hipLaunchKernelGGL((colwise_bwd_kernel<float, 2>), grid, dim3(256), 0, stream, (const float*)dy, (const float*)x, bias, (float*)dx, workspace, rows, C);
-  else if (dtype == BB_BF16 && act == 0)
-    hipLaunchKernelGGL((colwise_bwd_kernel<bf16_raw, 0>), grid, dim3(256), 0, stream, (const bf16_raw*)dy, (const bf16_raw*)x, bias, (bf16_raw*)dx, workspace, rows, C);
-  else if (dtype == BB_BF16)
-    hipLaunchKernelGGL((colwise_bwd_kernel<bf16_raw, 2>), grid, dim3(256), 0, stream, (const bf16_raw*)dy, (const bf16_raw*)x, bias, (bf16_raw*)dx, workspace, rows, C);
-  else {
-    bb_set_error("bias_act_bwd: dtype %d unsupported", dtype);
-    return BB_EUNSUPPORTED;
-  }
+  const bool type_ok = bb_with_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    bb_with_int<0, 1>(act, [&](auto a) {
+      constexpr int MODE = decltype(a)::value == 0 ? 0 : 2;      // of colwise_bwd_kernel: 0 erf-GELU, 2 ReLU
+      hipLaunchKernelGGL((colwise_bwd_kernel<T, MODE>), grid, dim3(256), 0, stream, (const T*)dy, (const T*)x, bias, (T*)dx, workspace, rows, C);
+    });
+  });
+  if (!type_ok) return bb_dtype_unsupported("bias_act_bwd", dtype);
   BB_CHECK_LAUNCH("bias_act_bwd");
   if (dbias) {
     launch_finalize(workspace, nb, 1, C, dbias, nullptr, nullptr, accumulate, stream);
@@ -1591,14 +1565,11 @@ BEVBERT_API int bevbert_colsum(const void* dy, float* out, float* workspace, int
   if (rows <= 0) return BB_OK;
   const int nb = colwise_blocks(rows);
   const dim3 grid(nb, (C + 1023) / 1024);
-  if (dtype == BB_F32)
-    hipLaunchKernelGGL((colwise_bwd_kernel<float, 1>), grid, dim3(256), 0, stream, (const float*)dy, nullptr, nullptr, nullptr, workspace, rows, C);
-  else if (dtype == BB_BF16)
-    hipLaunchKernelGGL((colwise_bwd_kernel<bf16_raw, 1>), grid, dim3(256), 0, stream, (const bf16_raw*)dy, nullptr, nullptr, nullptr, workspace, rows, C);
-  else {
-    bb_set_error("colsum: dtype %d unsupported", dtype);
-    return BB_EUNSUPPORTED;
-  }
+  const bool type_ok = bb_with_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((colwise_bwd_kernel<T, 1>), grid, dim3(256), 0, stream, (const T*)dy, nullptr, nullptr, nullptr, workspace, rows, C);
+  });
+  if (!type_ok) return bb_dtype_unsupported("colsum", dtype);
   BB_CHECK_LAUNCH("colsum");
   launch_finalize(workspace, nb, 1, C, out, nullptr, nullptr, accumulate, stream);
   BB_CHECK_LAUNCH("colsum finalize");
@@ -1611,14 +1582,11 @@ BEVBERT_API int bevbert_colsum_partials(const void* dy, float* partials, int row
   BB_REQUIRE(C % 4 == 0 && rows > 0, "colsum_partials: C=%d must be a multiple of 4, rows=%d positive", C, rows);
   const int nb = colwise_blocks(rows);
   const dim3 grid(nb, (C + 1023) / 1024);
-  if (dtype == BB_F32)
-    hipLaunchKernelGGL((colwise_bwd_kernel<float, 1>), grid, dim3(256), 0, stream, (const float*)dy, nullptr, nullptr, nullptr, partials, rows, C);
-  else if (dtype == BB_BF16)
-    hipLaunchKernelGGL((colwise_bwd_kernel<bf16_raw, 1>), grid, dim3(256), 0, stream, (const bf16_raw*)dy, nullptr, nullptr, nullptr, partials, rows, C);
-  else {
-    bb_set_error("colsum_partials: dtype %d unsupported", dtype);
-    return BB_EUNSUPPORTED;
-  }
+  const bool type_ok = bb_with_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((colwise_bwd_kernel<T, 1>), grid, dim3(256), 0, stream, (const T*)dy, nullptr, nullptr, nullptr, partials, rows, C);
+  });
+  if (!type_ok) return bb_dtype_unsupported("colsum_partials", dtype);
   BB_CHECK_LAUNCH("colsum_partials");
   return BB_OK;
 }
@@ -1647,14 +1615,11 @@ BEVBERT_API int bevbert_segment_wsum(const void* src, const int* rowptr, const i
                                      int out_rows, int H, int dtype, hipStream_t stream) {
   BB_REQUIRE(H % 4 == 0, "segment_wsum: H=%d must be a multiple of 4", H);
   if (out_rows <= 0) return BB_OK;
-  if (dtype == BB_F32)
-    hipLaunchKernelGGL(gather_wsum_kernel<float>, dim3(out_rows), dim3(192), 0, stream, (const float*)src, rowptr, idx, w, (float*)out, H);
-  else if (dtype == BB_BF16)
-    hipLaunchKernelGGL(gather_wsum_kernel<bf16_raw>, dim3(out_rows), dim3(192), 0, stream, (const bf16_raw*)src, rowptr, idx, w, (bf16_raw*)out, H);
-  else {
-    bb_set_error("segment_wsum: dtype %d unsupported", dtype);
-    return BB_EUNSUPPORTED;
-  }
+  const bool type_ok = bb_with_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(gather_wsum_kernel<T>, dim3(out_rows), dim3(192), 0, stream, (const T*)src, rowptr, idx, w, (T*)out, H);
+  });
+  if (!type_ok) return bb_dtype_unsupported("segment_wsum", dtype);
   BB_CHECK_LAUNCH("segment_wsum");
   return BB_OK;
 }
@@ -1665,14 +1630,11 @@ BEVBERT_API int bevbert_accum_partials(const void* partials, float* sink, int S,
   if (n == 0) return BB_OK;
   size_t nb = ((size_t)n / 4 + 255) / 256;
   if (nb > 8192) nb = 8192;
-  if (dtype == BB_F32)
-    hipLaunchKernelGGL(accum_partials_kernel<float>, dim3(nb), dim3(256), 0, stream, (const float*)partials, sink, S, (size_t)n / 4);
-  else if (dtype == BB_BF16)
-    hipLaunchKernelGGL(accum_partials_kernel<bf16_raw>, dim3(nb), dim3(256), 0, stream, (const bf16_raw*)partials, sink, S, (size_t)n / 4);
-  else {
-    bb_set_error("accum_partials: dtype %d unsupported", dtype);
-    return BB_EUNSUPPORTED;
-  }
+  const bool type_ok = bb_with_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(accum_partials_kernel<T>, dim3(nb), dim3(256), 0, stream, (const T*)partials, sink, S, (size_t)n / 4);
+  });
+  if (!type_ok) return bb_dtype_unsupported("accum_partials", dtype);
   BB_CHECK_LAUNCH("accum_partials");
   return BB_OK;
 }
@@ -1682,14 +1644,11 @@ BEVBERT_API int bevbert_rows_gather(const void* src, const int64_t* ids, void* o
   BB_REQUIRE(H % 4 == 0 && H > 0, "rows_gather: H=%d must be a positive multiple of 4", H);
   if (rows <= 0) return BB_OK;
   const int nt = H / 4 >= 256 ? 256 : (H / 4 + 63) / 64 * 64;
-  if (dtype == BB_F32)
-    hipLaunchKernelGGL(rows_gather_kernel<float>, dim3(rows), dim3(nt), 0, stream, (const float*)src, ids, (float*)out, H);
-  else if (dtype == BB_BF16)
-    hipLaunchKernelGGL(rows_gather_kernel<bf16_raw>, dim3(rows), dim3(nt), 0, stream, (const bf16_raw*)src, ids, (bf16_raw*)out, H);
-  else {
-    bb_set_error("rows_gather: dtype %d unsupported", dtype);
-    return BB_EUNSUPPORTED;
-  }
+  const bool type_ok = bb_with_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(rows_gather_kernel<T>, dim3(rows), dim3(nt), 0, stream, (const T*)src, ids, (T*)out, H);
+  });
+  if (!type_ok) return bb_dtype_unsupported("rows_gather", dtype);
   BB_CHECK_LAUNCH("rows_gather");
   return BB_OK;
 }
@@ -1698,18 +1657,13 @@ BEVBERT_API int bevbert_rows_scatter(const int64_t* ids, const void* d, void* ou
                                      hipStream_t stream) {
   BB_REQUIRE(H % 4 == 0 && H <= 256 * EG_MAXJ, "rows_scatter: H=%d must be a multiple of 4 and <= %d", H, 256 * EG_MAXJ);
   if (rows <= 0) return BB_OK;
-  if (dtype == BB_F32 && accumulate)
-    hipLaunchKernelGGL((embedding_grad_kernel<float, float, true>), dim3(rows), dim3(256), 0, stream, ids, (const float*)d, (float*)out, rows, H, -1);
-  else if (dtype == BB_F32)
-    hipLaunchKernelGGL((embedding_grad_kernel<float, float, false>), dim3(rows), dim3(256), 0, stream, ids, (const float*)d, (float*)out, rows, H, -1);
-  else if (dtype == BB_BF16 && accumulate)
-    hipLaunchKernelGGL((embedding_grad_kernel<bf16_raw, bf16_raw, true>), dim3(rows), dim3(256), 0, stream, ids, (const bf16_raw*)d, (bf16_raw*)out, rows, H, -1);
-  else if (dtype == BB_BF16)
-    hipLaunchKernelGGL((embedding_grad_kernel<bf16_raw, bf16_raw, false>), dim3(rows), dim3(256), 0, stream, ids, (const bf16_raw*)d, (bf16_raw*)out, rows, H, -1);
-  else {
-    bb_set_error("rows_scatter: dtype %d unsupported", dtype);
-    return BB_EUNSUPPORTED;
-  }
+  const bool type_ok = bb_with_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    bb_with_bool(accumulate != 0, [&](auto accum) {
+      hipLaunchKernelGGL((embedding_grad_kernel<T, T, decltype(accum)::value>), dim3(rows), dim3(256), 0, stream, ids, (const T*)d, (T*)out, rows, H, -1);
+    });
+  });
+  if (!type_ok) return bb_dtype_unsupported("rows_scatter", dtype);
   BB_CHECK_LAUNCH("rows_scatter");
   return BB_OK;
 }
@@ -1718,16 +1672,11 @@ BEVBERT_API int bevbert_embedding_grad(const int64_t* ids, const void* d, float*
                                        int padding_idx, int dtype, hipStream_t stream) {
   BB_REQUIRE(H % 4 == 0 && H <= 256 * EG_MAXJ, "embedding_grad: H=%d must be a multiple of 4 and <= %d", H, 256 * EG_MAXJ);
   if (rows <= 0) return BB_OK;
-  if (dtype == BB_F32)
-    hipLaunchKernelGGL(embedding_grad_kernel<float>, dim3(rows), dim3(256), 0, stream, ids, (const float*)d, table_grad, rows, H,
-                       padding_idx);
-  else if (dtype == BB_BF16)
-    hipLaunchKernelGGL(embedding_grad_kernel<bf16_raw>, dim3(rows), dim3(256), 0, stream, ids, (const bf16_raw*)d, table_grad,
-                       rows, H, padding_idx);
-  else {
-    bb_set_error("embedding_grad: dtype %d unsupported", dtype);
-    return BB_EUNSUPPORTED;
-  }
+  const bool type_ok = bb_with_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(embedding_grad_kernel<T>, dim3(rows), dim3(256), 0, stream, ids, (const T*)d, table_grad, rows, H, padding_idx);
+  });
+  if (!type_ok) return bb_dtype_unsupported("embedding_grad", dtype);
   BB_CHECK_LAUNCH("embedding_grad");
   return BB_OK;
 }
@@ -1741,16 +1690,12 @@ BEVBERT_API int bevbert_embedding_grad_sliced(const int64_t* ids, const void* d,
   BB_REQUIRE(slices <= 65535, "embedding_grad_sliced: %d slices exceed the grid limit", slices);
   const int nt = H / 4 < 256 ? ((H / 4 + 63) / 64) * 64 : 256;
   const dim3 grid(table_rows, slices);
-  if (dtype == BB_F32)
-    hipLaunchKernelGGL(embedding_grad_sliced_kernel<float>, grid, dim3(nt), 0, stream, ids, (const float*)d, partials, rows, H,
-                       rows_per_slice, table_rows);
-  else if (dtype == BB_BF16)
-    hipLaunchKernelGGL(embedding_grad_sliced_kernel<bf16_raw>, grid, dim3(nt), 0, stream, ids, (const bf16_raw*)d, partials,
-                       rows, H, rows_per_slice, table_rows);
-  else {
-    bb_set_error("embedding_grad_sliced: dtype %d unsupported", dtype);
-    return BB_EUNSUPPORTED;
-  }
+  const bool type_ok = bb_with_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(embedding_grad_sliced_kernel<T>, grid, dim3(nt), 0, stream, ids, (const T*)d, partials, rows, H, rows_per_slice,
+                       table_rows);
+  });
+  if (!type_ok) return bb_dtype_unsupported("embedding_grad_sliced", dtype);
   BB_CHECK_LAUNCH("embedding_grad_sliced");
   return BB_OK;
 }
@@ -1784,11 +1729,11 @@ BEVBERT_API int bevbert_cast_f32(const float* src, void* dst, int64_t n, int dst
   if (n == 0) return BB_OK;
   size_t nb = ((size_t)n / 4 + 255) / 256;
   if (nb > 8192) nb = 8192;
-  if (dst_dtype == BB_BF16)
-    hipLaunchKernelGGL(cast_f32_kernel<bf16_raw>, dim3(nb), dim3(256), 0, stream, src, (bf16_raw*)dst, (size_t)n / 4);
-  else if (dst_dtype == BB_F16)
-    hipLaunchKernelGGL(cast_f32_kernel<_Float16>, dim3(nb), dim3(256), 0, stream, src, (_Float16*)dst, (size_t)n / 4);
-  else {
+  const bool type_ok = bb_with_type_of<bf16_raw, _Float16>(dst_dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(cast_f32_kernel<T>, dim3(nb), dim3(256), 0, stream, src, (T*)dst, (size_t)n / 4);
+  });
+  if (!type_ok) {                                             // its own wording: "dst dtype"
     bb_set_error("cast_f32: dst dtype %d unsupported", dst_dtype);
     return BB_EUNSUPPORTED;
   }

@@ -85,17 +85,13 @@ BEVBERT_API int bevbert_sap_loss_fwd(const void* global_raw, const void* local_r
                                      float* dL, float* dF, int B, int G, int K, int P, int dtype, hipStream_t stream) {
   BB_REQUIRE(G >= 1 && G <= 64 && K >= 1 && K <= 62, "sap_loss: G=%d (<= 64) / K=%d (<= 62) out of range", G, K);
   if (B <= 0) return BB_OK;
-#define GO(T)                                                                                                         \
-  hipLaunchKernelGGL(sap_loss_kernel<T>, dim3(B), dim3(64), 0, stream, (const T*)global_raw, (const T*)local_raw,      \
-                     (const T*)fuse_raw, visited, gmap_lens, nav_masks, cand_idxs, src, vis_c, global_labels,         \
-                     local_labels, loss, dG, dL, dF, G, K, P)
-  if (dtype == BB_F32) GO(float);
-  else if (dtype == BB_BF16) GO(bf16_raw);
-  else {
-    bb_set_error("sap_loss: dtype %d unsupported", dtype);
-    return BB_EUNSUPPORTED;
-  }
-#undef GO
+  const bool type_ok = bb_with_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(sap_loss_kernel<T>, dim3(B), dim3(64), 0, stream, (const T*)global_raw, (const T*)local_raw,
+                       (const T*)fuse_raw, visited, gmap_lens, nav_masks, cand_idxs, src, vis_c, global_labels, local_labels,
+                       loss, dG, dL, dF, G, K, P);
+  });
+  if (!type_ok) return bb_dtype_unsupported("sap_loss", dtype);
   BB_CHECK_LAUNCH("sap_loss_fwd");
   return BB_OK;
 }
@@ -105,16 +101,12 @@ BEVBERT_API int bevbert_sap_loss_bwd(const float* dG, const float* dL, const flo
                                      int dtype, hipStream_t stream) {
   BB_REQUIRE(G >= 1 && G <= 64 && K >= 1 && K <= 62, "sap_loss: G=%d (<= 64) / K=%d (<= 62) out of range", G, K);
   if (B <= 0) return BB_OK;
-#define GO(T)                                                                                                     \
-  hipLaunchKernelGGL(sap_loss_grad_kernel<T>, dim3(B), dim3(64), 0, stream, dG, dL, dF, dloss, (T*)d_global_raw, \
-                     (T*)d_local_raw, (T*)d_fuse_raw, G, K)
-  if (dtype == BB_F32) GO(float);
-  else if (dtype == BB_BF16) GO(bf16_raw);
-  else {
-    bb_set_error("sap_loss: dtype %d unsupported", dtype);
-    return BB_EUNSUPPORTED;
-  }
-#undef GO
+  const bool type_ok = bb_with_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(sap_loss_grad_kernel<T>, dim3(B), dim3(64), 0, stream, dG, dL, dF, dloss, (T*)d_global_raw,
+                       (T*)d_local_raw, (T*)d_fuse_raw, G, K);
+  });
+  if (!type_ok) return bb_dtype_unsupported("sap_loss", dtype);
   BB_CHECK_LAUNCH("sap_loss_bwd");
   return BB_OK;
 }
@@ -200,15 +192,11 @@ BEVBERT_API int bevbert_cross_entropy_fwd(const void* logits, const int64_t* tar
   BB_REQUIRE(C >= 1, "cross_entropy: C=%d", C);
   if (rows <= 0) return BB_OK;
   BB_REQUIRE(((uintptr_t)logits % 16) == 0, "cross_entropy: logits must be 16-byte aligned%s", "");
-  if (dtype == BB_F32)
-    hipLaunchKernelGGL(ce_fwd_kernel<float>, dim3(rows), dim3(256), 0, stream, (const float*)logits, target, loss, lse, C);
-  else if (dtype == BB_BF16)
-    hipLaunchKernelGGL(ce_fwd_kernel<bf16_raw>, dim3(rows), dim3(256), 0, stream, (const bf16_raw*)logits, target, loss,
-                       lse, C);
-  else {
-    bb_set_error("cross_entropy: dtype %d unsupported", dtype);
-    return BB_EUNSUPPORTED;
-  }
+  const bool type_ok = bb_with_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(ce_fwd_kernel<T>, dim3(rows), dim3(256), 0, stream, (const T*)logits, target, loss, lse, C);
+  });
+  if (!type_ok) return bb_dtype_unsupported("cross_entropy", dtype);
   BB_CHECK_LAUNCH("cross_entropy_fwd");
   return BB_OK;
 }
@@ -218,16 +206,11 @@ BEVBERT_API int bevbert_cross_entropy_bwd(const void* logits, const int64_t* tar
   if (rows <= 0) return BB_OK;
   BB_REQUIRE(((uintptr_t)logits % 16) == 0 && ((uintptr_t)dlogits % 16) == 0,
              "cross_entropy: logits / dlogits must be 16-byte aligned%s", "");
-  if (dtype == BB_F32)
-    hipLaunchKernelGGL(ce_bwd_kernel<float>, dim3(rows), dim3(256), 0, stream, (const float*)logits, target, lse, dloss,
-                       (float*)dlogits, C);
-  else if (dtype == BB_BF16)
-    hipLaunchKernelGGL(ce_bwd_kernel<bf16_raw>, dim3(rows), dim3(256), 0, stream, (const bf16_raw*)logits, target, lse,
-                       dloss, (bf16_raw*)dlogits, C);
-  else {
-    bb_set_error("cross_entropy: dtype %d unsupported", dtype);
-    return BB_EUNSUPPORTED;
-  }
+  const bool type_ok = bb_with_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(ce_bwd_kernel<T>, dim3(rows), dim3(256), 0, stream, (const T*)logits, target, lse, dloss, (T*)dlogits, C);
+  });
+  if (!type_ok) return bb_dtype_unsupported("cross_entropy", dtype);
   BB_CHECK_LAUNCH("cross_entropy_bwd");
   return BB_OK;
 }

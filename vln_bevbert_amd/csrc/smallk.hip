@@ -276,18 +276,15 @@ BEVBERT_API int bevbert_smallk_linear_layernorm_fwd(const float* feat, const flo
   if (nb > 1024) nb = 1024;
   const size_t lds = (size_t)K * H * sizeof(float);
   BB_REQUIRE(lds <= 64 * 1024, "smallk_linear_layernorm_fwd: K=%d x H=%d needs more than 64 KB of LDS", K, H);
-#define GO(TT, N)                                                                                                     \
-  hipLaunchKernelGGL((smallk_ln_fwd_kernel<TT, N>), dim3(nb), dim3(256), lds, stream, feat, weight, bias, gamma, beta,  \
-                     (const TT*)post1, (const TT*)table, idx, (TT*)y, mean, rstd, rows, K, eps)
-  if (dtype == BB_F32) {
-    switch (H / 256) { case 1: GO(float, 1); break; case 2: GO(float, 2); break; case 3: GO(float, 3); break; default: GO(float, 4); }
-  } else if (dtype == BB_BF16) {
-    switch (H / 256) { case 1: GO(bf16_raw, 1); break; case 2: GO(bf16_raw, 2); break; case 3: GO(bf16_raw, 3); break; default: GO(bf16_raw, 4); }
-  } else {
-    bb_set_error("smallk_linear_layernorm_fwd: dtype %d unsupported", dtype);
-    return BB_EUNSUPPORTED;
-  }
-#undef GO
+  const bool type_ok = bb_with_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    // H is one of the four (checked above); listed downwards (common.h), the kernels keep their order in the code object
+    bb_with_width<4, 3, 2, 1>(H, [&](auto nv) {
+      hipLaunchKernelGGL((smallk_ln_fwd_kernel<T, decltype(nv)::value>), dim3(nb), dim3(256), lds, stream, feat, weight, bias, gamma,
+                         beta, (const T*)post1, (const T*)table, idx, (T*)y, mean, rstd, rows, K, eps);
+    });
+  });
+  if (!type_ok) return bb_dtype_unsupported("smallk_linear_layernorm_fwd", dtype);
   BB_CHECK_LAUNCH("smallk_linear_layernorm_fwd");
   return BB_OK;
 }
@@ -304,18 +301,14 @@ BEVBERT_API int bevbert_smallk_linear_layernorm_bwd(const void* dy, const float*
   const int nb = sk_bwd_blocks(rows);
   const size_t lds = ((size_t)K * H + (size_t)SK_R * H + (size_t)SK_R * SK_MAXK) * sizeof(float);
   BB_REQUIRE(lds <= 64 * 1024, "smallk_linear_layernorm_bwd: K=%d x H=%d needs more than 64 KB of LDS", K, H);
-#define GO(TT, N)                                                                                                     \
-  hipLaunchKernelGGL((smallk_ln_bwd_kernel<TT, N>), dim3(nb), dim3(256), lds, stream, (const TT*)dy, feat, weight, bias, \
-                     mean, rstd, gamma, workspace, rows, K)
-  if (dtype == BB_F32) {
-    switch (H / 256) { case 1: GO(float, 1); break; case 2: GO(float, 2); break; case 3: GO(float, 3); break; default: GO(float, 4); }
-  } else if (dtype == BB_BF16) {
-    switch (H / 256) { case 1: GO(bf16_raw, 1); break; case 2: GO(bf16_raw, 2); break; case 3: GO(bf16_raw, 3); break; default: GO(bf16_raw, 4); }
-  } else {
-    bb_set_error("smallk_linear_layernorm_bwd: dtype %d unsupported", dtype);
-    return BB_EUNSUPPORTED;
-  }
-#undef GO
+  const bool type_ok = bb_with_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    bb_with_width<4, 3, 2, 1>(H, [&](auto nv) {
+      hipLaunchKernelGGL((smallk_ln_bwd_kernel<T, decltype(nv)::value>), dim3(nb), dim3(256), lds, stream, (const T*)dy, feat, weight,
+                         bias, mean, rstd, gamma, workspace, rows, K);
+    });
+  });
+  if (!type_ok) return bb_dtype_unsupported("smallk_linear_layernorm_bwd", dtype);
   BB_CHECK_LAUNCH("smallk_linear_layernorm_bwd");
   hipLaunchKernelGGL(smallk_finalize_kernel, dim3(H / 64, K + 3), dim3(256), 0, stream, workspace, nb, K, H,
                      dweight, dgamma, dbeta, dbias);

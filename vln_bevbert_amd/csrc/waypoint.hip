@@ -62,11 +62,10 @@ BEVBERT_API int bevbert_wp_ring_attn(const void* qkv, void* out, int B, int nh, 
   BB_REQUIRE(qkv && out, "wp_ring_attn: null tensor%s", "");
   const int pairs = B * nh;
   const dim3 grid((pairs + 3) / 4), block(256);
-  if (dtype == BB_F32)
-    hipLaunchKernelGGL(wp_ring_attn_kernel<float>, grid, block, 0, stream, (const float*)qkv, (float*)out, pairs, nh, scale);
-  else
-    hipLaunchKernelGGL(wp_ring_attn_kernel<bf16_raw>, grid, block, 0, stream, (const bf16_raw*)qkv, (bf16_raw*)out, pairs,
-                       nh, scale);
+  bb_with_type(dtype, [&](auto t) {                     // one of the two: checked above
+    using T = decltype(t);
+    hipLaunchKernelGGL(wp_ring_attn_kernel<T>, grid, block, 0, stream, (const T*)qkv, (T*)out, pairs, nh, scale);
+  });
   BB_CHECK_LAUNCH("wp_ring_attn");
   return BB_OK;
 }
@@ -353,15 +352,12 @@ BEVBERT_API int bevbert_wp_pano_inputs(const void* rgb_embeds, const void* depth
   BB_REQUIRE(rgb_embeds && depth_embeds && cand_count && cand_img_idx && cand_angle_fts && pano_angle_fts && pano_rgb &&
                  pano_depth && rgb_fts && dep_fts && loc_fts && nav_types && view_lens, "wp_pano_inputs: null tensor%s", "");
   const dim3 grid(B, WP_VIEWS + WP_L), block(128);
-  if (dtype == BB_F32)
-    hipLaunchKernelGGL(wp_pano_inputs_kernel<float>, grid, block, 0, stream, (const float*)rgb_embeds,
-                       (const float*)depth_embeds, cand_count, cand_img_idx, cand_angle_fts, pano_angle_fts,
-                       (float*)pano_rgb, (float*)pano_depth, (float*)rgb_fts, (float*)dep_fts, loc_fts, nav_types, view_lens);
-  else
-    hipLaunchKernelGGL(wp_pano_inputs_kernel<bf16_raw>, grid, block, 0, stream, (const bf16_raw*)rgb_embeds,
-                       (const bf16_raw*)depth_embeds, cand_count, cand_img_idx, cand_angle_fts, pano_angle_fts,
-                       (bf16_raw*)pano_rgb, (bf16_raw*)pano_depth, (bf16_raw*)rgb_fts, (bf16_raw*)dep_fts, loc_fts,
-                       nav_types, view_lens);
+  bb_with_type(dtype, [&](auto t) {                     // one of the two: checked above
+    using T = decltype(t);
+    hipLaunchKernelGGL(wp_pano_inputs_kernel<T>, grid, block, 0, stream, (const T*)rgb_embeds, (const T*)depth_embeds, cand_count,
+                       cand_img_idx, cand_angle_fts, pano_angle_fts, (T*)pano_rgb, (T*)pano_depth, (T*)rgb_fts, (T*)dep_fts,
+                       loc_fts, nav_types, view_lens);
+  });
   BB_CHECK_LAUNCH("wp_pano_inputs");
   return BB_OK;
 }
