@@ -648,6 +648,40 @@ int bevbert_ce_remember(const bevbert_ce_state* st, const uint8_t* live, const v
 int bevbert_ce_bev_select(const bevbert_ce_state* st, const uint8_t* live, int order, int R, int* rows, uint8_t* row_live,
                           hipStream_t stream);
 
+/* ---- CLIP vision transformer (csrc/vit.hip, clip_vit.py): forward-only row kernels ------------------------------------
+ * Rows are (rows, H) row-major, H in {256, 512, 768, 1024}; the residual stream z32 is fp32 whatever `dtype` (the
+ * compute dtype of the GEMM operands: BB_F32 or BB_BF16). */
+
+/* ConvertImageDtype + Normalize + conv1's im2col: images (n_src, R, R, 3) u8 -> out (N * g * g, 3 * P * P) dtype with
+ * g = R / P, P in {16, 32}, column order (c, ky, kx); output image i reads input image view_map[i] (NULL: i; an index
+ * outside [0, n_src) gives rows of zeros).  value = (float(u8) / 255 - mean_c) / std_c, each operation rounded to nearest;
+ * mean_std: six HOST floats, mean[3] then std[3]. */
+int bevbert_vit_patchify(const uint8_t* images, const int* view_map, void* out, int N, int n_src, int R, int P,
+                         const float* mean_std, int dtype, hipStream_t stream);
+
+/* Token assembly + ln_pre + ln_1 of block 0: row n * L + t is class_embedding + pos[0] for t = 0 and
+ * conv_out[n * (L - 1) + t - 1] + pos[t] otherwise (conv_out (N * (L - 1), H) dtype; class_embedding (H), pos (L, H) f32);
+ * z32 (N * L, H) f32 = LayerNorm(row; gamma_pre, beta_pre), y (N * L, H) dtype = LayerNorm(z32; gamma1, beta1). */
+int bevbert_vit_embed_prenorm(const void* conv_out, const float* class_embedding, const float* pos, const float* gamma_pre,
+                              const float* beta_pre, const float* gamma1, const float* beta1, float* z32, void* y, int N,
+                              int L, int H, float eps, int dtype, hipStream_t stream);
+
+/* z = z32 + (x + bias) with x (rows, H) dtype.  final_form = 0: z32 <- z in place, y (rows, H) dtype = LayerNorm(z).
+ * final_form = 1 (rows = N * L): rows t > 0 of every image go to x_patch (N, L - 1, H) f32 unnormalised, the class rows
+ * t = 0 through LayerNorm to y (N, H) dtype; z32 is left as it was. */
+int bevbert_vit_bias_residual_prenorm(float* z32, const void* x, const float* bias, const float* gamma, const float* beta,
+                                      void* y, float* x_patch, int rows, int L, int H, float eps, int final_form, int dtype,
+                                      hipStream_t stream);
+
+/* QuickGELU: t = x + bias, y = t * sigmoid(1.702 t); (rows, C) dtype, C % 4 == 0, bias (C) f32; finite for every finite t;
+ * y may be x. */
+int bevbert_vit_bias_quickgelu(const void* x, const float* bias, void* y, int rows, int C, int dtype, hipStream_t stream);
+
+/* AdaptiveAvgPool2d((G, G)) of depth (n_src, Hd, Wd) f32 -> out (N, G, G) f32, windows as torch defines them; view_map as
+ * in bevbert_vit_patchify. */
+int bevbert_depth_grid_pool(const float* depth, const int* view_map, float* out, int N, int n_src, int Hd, int Wd, int G,
+                            hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -68,6 +68,13 @@ inline int bb_dtype_unsupported(const char* name, int dtype) {
   return BB_EUNSUPPORTED;
 }
 
+// row groups of a purely elementwise row kernel (no partial rows to bound): 8 rows each, at most 4096 groups
+static inline int elementwise_row_groups(int rows) {
+  int nb = (rows + 7) / 8;
+  if (nb > 4096) nb = 4096;
+  return nb < 1 ? 1 : nb;
+}
+
 // ---- scalar conversions (round-to-nearest-even, NaN preserved) ----------------------------
 __device__ __forceinline__ float bf16_to_f32(bf16_raw v) { return __uint_as_float(((uint32_t)v) << 16); }
 // gfx950 converts in hardware (v_cvt_pk_bf16_f32, round-to-nearest-even): let the compiler pick it

@@ -1375,13 +1375,6 @@ static int colwise_blocks(int rows) {
 // at two waves per SIMD: up to 512 of them on the 256 CUs, i.e. up to 5 120 rows.  Larger launches keep the plain kernel.
 static bool ln_res32_bwd_loads_ahead(int nblocks) { return nblocks <= 512; }
 
-// row groups of a purely elementwise row kernel (no partial rows to bound): 8 rows each, at most 4096 groups
-static int elementwise_row_groups(int rows) {
-  int nb = (rows + 7) / 8;
-  if (nb > 4096) nb = 4096;
-  return nb < 1 ? 1 : nb;
-}
-
 // workspace: >= bevbert_colsum_workspace_floats(3*H) floats
 BEVBERT_API int64_t bevbert_colsum_workspace_floats(int total_cols) { return (int64_t)colwise_max_blocks() * total_cols; }
 
