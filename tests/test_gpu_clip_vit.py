@@ -120,6 +120,24 @@ def test_bias_residual_prenorm_against_fp64(rows, H, dtype):
     assert ez < LN_TOL[torch.float32] and ey < LN_TOL[dtype]
 
 
+@pytest.mark.parametrize("H", [256, 768, 1024])
+@pytest.mark.parametrize("rows", [1, 5, 9])
+def test_bias_residual_prenorm_gives_the_bits_of_the_plain_layernorm(rows, H):
+    """The ViT kernel and ln_fwd_kernel share one row body (ln_row_stats / ln_norm4): on the z32 the ViT kernel leaves,
+    ops.layernorm gives the same fp32 bits, and for bf16 operands their bf16 rounding."""
+    from vln_bevbert_amd import ops
+    gen = torch.Generator().manual_seed(rows * 11 + H)
+    z0 = (2 * torch.randn(rows, H, generator=gen)).to(DEV)
+    x32 = torch.randn(rows, H, generator=gen).to(DEV)
+    ((g, b),), (bias,) = _params(H, gen, 1)
+    for x in (x32, x32.to(torch.bfloat16)):
+        z32 = z0.clone()
+        y = V.bias_residual_prenorm(z32, x, bias, g, b)
+        plain = ops.layernorm(z32, g, b, V.LN_EPS)
+        assert plain.dtype == torch.float32 and y.dtype == x.dtype
+        assert torch.equal(y, plain.to(x.dtype)), (rows, H, x.dtype)
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("H", [256, 768, 1024])
 @pytest.mark.parametrize("N,L", [(1, 197), (3, 197), (2, 50)])

@@ -441,6 +441,33 @@ def test_smallk_linear_layernorm_plus(ops, dtype, rows, K, T):
     assert torch.equal(y2, y) and torch.equal(g2, g)
 
 
+@pytest.mark.parametrize("H", [256, 768])
+def test_smallk_linear_layernorm_gives_the_bits_of_the_plain_layernorm(ops, H):
+    """smallk_ln_fwd_kernel and ln_fwd_kernel share one row body.  With one-hot feature rows the in-kernel projection is
+    exactly bias + W[:, k] (the fma with 1 rounds once, those with 0 change nothing), so with a zero post1 and no table
+    the output is bit for bit the plain LayerNorm of that row."""
+    from vln_bevbert_amd.arena import ParamArena
+    torch.manual_seed(H)
+    rows, K = 9, 7
+
+    class M(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.lin, self.ln = torch.nn.Linear(K, H), torch.nn.LayerNorm(H, eps=1e-12)
+    m = M()
+    with torch.no_grad():
+        m.ln.weight.uniform_(0.5, 1.5); m.ln.bias.normal_(0, 0.3)
+    ParamArena(m, DEV, torch.float32)
+    k_of_row = torch.arange(rows, device=DEV) % K
+    feat = torch.nn.functional.one_hot(k_of_row, K).float()
+    post1 = torch.zeros(rows, H, device=DEV)
+    assert ops.smallk_linear_layernorm_plus_supported(feat, m.lin, m.ln, post1)
+    with torch.no_grad():
+        y = ops.smallk_linear_layernorm_plus(feat, m.lin, m.ln, 1e-12, post1)
+        plain = ops.layernorm(m.lin.bias + m.lin.weight.t()[k_of_row], m.ln.weight, m.ln.bias, 1e-12)
+    assert torch.equal(y, plain)
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_semantic_head_loss_select_and_bce(ops, dtype):
     """ops.sem_select + ops.bce_rows + ops.weighted_mean (pretrain_cmt.py:391-441 on a static batch): the cells with both

@@ -296,6 +296,20 @@ def test_res32_layernorm_bwd_few_rows(ops, H, outs, p, res):
         assert max(errs["dgamma"], errs["dbeta"], errs["dbias"]) <= 1e-4, (rows, errs)
 
 
+@pytest.mark.parametrize("H", [256, 768])
+@pytest.mark.parametrize("rows", [1, 5])
+def test_res32_layernorm_fwd_gives_the_bits_of_the_plain_layernorm(ops, rows, H):
+    """ln_res32_fwd_kernel and ln_fwd_kernel share one row body: without dropout, y32 is bit for bit the plain fp32
+    LayerNorm of (x + bias) + residual summed in that order, and y16 its bf16 rounding."""
+    from vln_bevbert_amd.ops_rowops import _BiasDropResLN32
+    rnd = _gen(rows * 17 + H)
+    x = rnd(rows, H).to(BF16)
+    residual, gamma, beta, bias = 2 * rnd(rows, H), 1 + 0.1 * rnd(H), 0.1 * rnd(H), 0.1 * rnd(H)
+    y16, y32 = _BiasDropResLN32.apply(x, bias, residual, gamma, beta, 1e-12, 0.0)
+    plain = ops.layernorm((x.float() + bias) + residual, gamma, beta, 1e-12)
+    assert torch.equal(y32, plain) and torch.equal(y16, plain.to(BF16))
+
+
 def _plain_step(ops, x, bias, residual, gamma, beta, dy, dz_add, p, seed):
     from vln_bevbert_amd.ops_rowops import _BiasDropResLN
     for t in (x, bias, residual, gamma, beta):

@@ -143,6 +143,36 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// ---- LayerNorm of a row held in registers ---------------------------------------------------
+// One wave owns a row of H = NV * 256 values, NV float4s per lane.  A kernel of the LayerNorm family takes its statistics
+// and its affine step from here, so that kernels that see the same row give the same bits.  ln_fwd_kernel,
+// ln_res32_fwd_kernel (rowops.hip) and smallk_ln_fwd_kernel (smallk.hip) still carry the text of ln_row_stats themselves:
+// called from here their rstd changes in the last bit (see ln_fwd_kernel).
+__device__ __forceinline__ void add4(float4& a, const float4 b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; }
+// two-pass variance, eps inside the square root
+template <int NV>
+__device__ __forceinline__ void ln_row_stats(const float4 (&v)[NV], float eps, float& mean, float& rstd) {
+  constexpr int H = NV * 256;
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
+  mean = wave_sum(s) * (1.0f / H);
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const float dx = v[i].x - mean, dy = v[i].y - mean, dz = v[i].z - mean, dw = v[i].w - mean;
+    q += (dx * dx + dy * dy) + (dz * dz + dw * dw);
+  }
+  rstd = rsqrtf(wave_sum(q) * (1.0f / H) + eps);
+}
+__device__ __forceinline__ float4 ln_norm4(float4 v, float mean, float rstd, const float* __restrict__ gamma,
+                                           const float* __restrict__ beta, int col) {
+  const float4 g = *reinterpret_cast<const float4*>(gamma + col);
+  const float4 b = *reinterpret_cast<const float4*>(beta + col);
+  return make_float4((v.x - mean) * rstd * g.x + b.x, (v.y - mean) * rstd * g.y + b.y, (v.z - mean) * rstd * g.z + b.z,
+                     (v.w - mean) * rstd * g.w + b.w);
+}
+
 // ---- counter-based dropout RNG --------------------------------------------------------------
 // keep(element) is a pure function of (seed, offset, element index), so a backward kernel regenerates the forward's
 // mask instead of storing it.  A launch folds (seed, offset) into one 32-bit site key on the host; on the device one
@@ -180,6 +210,17 @@ __device__ __forceinline__ bool bb_keep_hi(uint32_t bits, uint32_t thr) { return
 __device__ __forceinline__ bool bb_keep(uint32_t key, uint32_t idx, uint32_t thr) {
   const uint32_t bits = bb_pair_bits(key, idx >> 1);
   return ((idx & 1u) ? (bits >> 16) : (bits & 0xffffu)) >= thr;
+}
+// the mask on four neighbouring elements (elem = the first one's index in the tensor, a multiple of 4: two index pairs);
+// forward and backward of a dropout site both come through here
+__device__ __forceinline__ float4 bb_drop4(float4 v, uint32_t elem, uint32_t key, uint32_t thr, float keep_scale) {
+  const uint32_t pr = elem >> 1;
+  const uint32_t b0 = bb_pair_bits(key, pr), b1 = bb_pair_bits(key, pr + 1);
+  v.x = bb_keep_lo(b0, thr) ? v.x * keep_scale : 0.f;
+  v.y = bb_keep_hi(b0, thr) ? v.y * keep_scale : 0.f;
+  v.z = bb_keep_lo(b1, thr) ? v.z * keep_scale : 0.f;
+  v.w = bb_keep_hi(b1, thr) ? v.w * keep_scale : 0.f;
+  return v;
 }
 
 // erf-GELU in a dozen instructions for the bf16 kernels (libm's erff costs ~45 VALU instructions per element with

@@ -20,6 +20,18 @@
 // LayerNorm forward:  z = dropout(x + bias) + residual ;  y = (z - mean) * rstd * gamma + beta
 // GATHER: x row = word[ids[row]] + pos[row % L] + type_row   (BertEmbeddings)
 // =============================================================================================
+// The input stage of one float4 chunk, shared by ln_fwd_kernel and ln_res32_fwd_kernel: bias, then the dropout mask (elem
+// = the chunk's first element index in the tensor), then the residual chunk r, which the caller has loaded through its
+// own storage type (has_res: there is one).
+__device__ __forceinline__ float4 ln_fwd_input(float4 a, const float* __restrict__ bias, int col, float drop_p, uint32_t elem,
+                                               uint32_t drop_key, uint32_t drop_thr, float keep_scale, bool has_res,
+                                               const float4 r) {
+  if (bias != nullptr) add4(a, *reinterpret_cast<const float4*>(bias + col));
+  if (drop_p > 0.f) a = bb_drop4(a, elem, drop_key, drop_thr, keep_scale);
+  if (has_res) add4(a, r);
+  return a;
+}
+
 template <typename T, int NV, bool GATHER>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, const float* __restrict__ bias,
                                                      const T* __restrict__ residual, const float* __restrict__ gamma,
@@ -50,24 +62,13 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, co
     } else {
       a = ld4<T>(x + (size_t)row * H + col);
     }
-    if (bias != nullptr) {
-      const float4 bb = *reinterpret_cast<const float4*>(bias + col);
-      a.x += bb.x; a.y += bb.y; a.z += bb.z; a.w += bb.w;
-    }
-    if (drop_p > 0.f) {
-      const uint32_t pr = ((uint32_t)row * H + col) >> 1;        // col % 4 == 0: two index pairs
-      const uint32_t b0 = bb_pair_bits(drop_key, pr), b1 = bb_pair_bits(drop_key, pr + 1);
-      a.x = bb_keep_lo(b0, drop_thr) ? a.x * keep_scale : 0.f;
-      a.y = bb_keep_hi(b0, drop_thr) ? a.y * keep_scale : 0.f;
-      a.z = bb_keep_lo(b1, drop_thr) ? a.z * keep_scale : 0.f;
-      a.w = bb_keep_hi(b1, drop_thr) ? a.w * keep_scale : 0.f;
-    }
-    if (residual != nullptr) {
-      const float4 r = ld4<T>(residual + (size_t)row * H + col);
-      a.x += r.x; a.y += r.y; a.z += r.z; a.w += r.w;
-    }
-    v[i] = a;
+    const bool has_res = residual != nullptr;
+    const float4 r = has_res ? ld4<T>(residual + (size_t)row * H + col) : make_float4(0.f, 0.f, 0.f, 0.f);
+    v[i] = ln_fwd_input(a, bias, col, drop_p, (uint32_t)row * H + col, drop_key, drop_thr, keep_scale, has_res, r);
   }
+  // The text of ln_row_stats (common.h), on purpose not a call: inlined from the helper the compiler contracts the sum of
+  // squares the other way round (which product of dx * dx + dy * dy goes into the fma), and rstd -- which the backward
+  // kernels and every replayed graph rely on -- differs in the last bit on some rows.  Keep the texts equal.
   float s = 0.f;
 #pragma unroll
   for (int i = 0; i < NV; ++i) s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
@@ -87,23 +88,11 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, co
   for (int i = 0; i < NV; ++i) {
     const int col = (i * 64 + lane) * 4;
     if (z_out != nullptr) st4<T>(z_out + (size_t)row * H + col, v[i]);
-    const float4 g = *reinterpret_cast<const float4*>(gamma + col);
-    const float4 b = *reinterpret_cast<const float4*>(beta + col);
-    float4 o;
-    o.x = (v[i].x - mean) * rstd * g.x + b.x;
-    o.y = (v[i].y - mean) * rstd * g.y + b.y;
-    o.z = (v[i].z - mean) * rstd * g.z + b.z;
-    o.w = (v[i].w - mean) * rstd * g.w + b.w;
+    float4 o = ln_norm4(v[i], mean, rstd, gamma, beta, col);
     if (!GATHER) {   // post-normalisation terms (bevbert_layernorm_post_fwd): y = LN(..) + post1 + post2, in that order --
       // the GATHER-only pointers carry them, so the plain variant costs two null tests
-      if (word != nullptr) {
-        const float4 r = ld4<T>(word + (size_t)row * H + col);
-        o.x += r.x; o.y += r.y; o.z += r.z; o.w += r.w;
-      }
-      if (pos != nullptr) {
-        const float4 r = ld4<T>(pos + (size_t)row * H + col);
-        o.x += r.x; o.y += r.y; o.z += r.z; o.w += r.w;
-      }
+      if (word != nullptr) add4(o, ld4<T>(word + (size_t)row * H + col));
+      if (pos != nullptr) add4(o, ld4<T>(pos + (size_t)row * H + col));
     }
     st4<T>(y + (size_t)row * H + col, o);
   }
@@ -123,29 +112,18 @@ __device__ __forceinline__ void ln_bwd_chunk_reduce(float4& d, const float4 zz, 
                                                     float4& ag, float4& ab, float& s1, float& s2) {
   xh = make_float4((zz.x - mu) * rs, (zz.y - mu) * rs, (zz.z - mu) * rs, (zz.w - mu) * rs);
   ag.x += d.x * xh.x; ag.y += d.y * xh.y; ag.z += d.z * xh.z; ag.w += d.w * xh.w;
-  ab.x += d.x; ab.y += d.y; ab.z += d.z; ab.w += d.w;
+  add4(ab, d);
   d.x *= g.x; d.y *= g.y; d.z *= g.z; d.w *= g.w;
   s1 += (d.x + d.y) + (d.z + d.w);
   s2 += (d.x * xh.x + d.y * xh.y) + (d.z * xh.z + d.w * xh.w);
 }
-// Second half, with s1 / s2 the row means: the chunk of dz ...
+// Second half, with s1 / s2 the row means: the chunk of dz; dx is dz through the forward's dropout mask (bb_drop4)
 __device__ __forceinline__ float4 ln_bwd_chunk_dz(const float4 d, const float4 xh, float rs, float s1, float s2) {
   float4 o;
   o.x = rs * (d.x - s1 - xh.x * s2);
   o.y = rs * (d.y - s1 - xh.y * s2);
   o.z = rs * (d.z - s1 - xh.z * s2);
   o.w = rs * (d.w - s1 - xh.w * s2);
-  return o;
-}
-// ... and of dx: dz through the forward's dropout mask (elem = the chunk's first element index in the tensor)
-__device__ __forceinline__ float4 ln_bwd_chunk_drop(float4 o, uint32_t elem, uint32_t drop_key, uint32_t drop_thr,
-                                                  float keep_scale) {
-  const uint32_t pr = elem >> 1;
-  const uint32_t b0 = bb_pair_bits(drop_key, pr), b1 = bb_pair_bits(drop_key, pr + 1);
-  o.x = bb_keep_lo(b0, drop_thr) ? o.x * keep_scale : 0.f;
-  o.y = bb_keep_hi(b0, drop_thr) ? o.y * keep_scale : 0.f;
-  o.z = bb_keep_lo(b1, drop_thr) ? o.z * keep_scale : 0.f;
-  o.w = bb_keep_hi(b1, drop_thr) ? o.w * keep_scale : 0.f;
   return o;
 }
 // The end of these kernels: the four waves' column partials folded through LDS in wave order into partials[block][3][H]
@@ -165,10 +143,7 @@ __device__ __forceinline__ void ln_bwd_store_partials(float4 (&s_red)[3][4][NV *
     const int which = k / (NV * 64), j = k % (NV * 64);
     float4 a = s_red[which][0][j];
 #pragma unroll
-    for (int w = 1; w < 4; ++w) {
-      const float4 t = s_red[which][w][j];
-      a.x += t.x; a.y += t.y; a.z += t.z; a.w += t.w;
-    }
+    for (int w = 1; w < 4; ++w) add4(a, s_red[which][w][j]);
     *reinterpret_cast<float4*>(partials + ((size_t)blockIdx.x * 3 + which) * H + j * 4) = a;
   }
 }
@@ -209,14 +184,12 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
     for (int i = 0; i < NV; ++i) {
       const int col = (i * 64 + lane) * 4;
       float4 o = ln_bwd_chunk_dz(d[i], xh[i], rs, s1, s2);
-      if (dz_add != nullptr) {       // z has a second consumer (pre-norm residual stream): its gradient joins here
-        const float4 e = ld4<T>(dz_add + (size_t)row * H + col);
-        o.x += e.x; o.y += e.y; o.z += e.z; o.w += e.w;
-      }
+      // z has a second consumer (pre-norm residual stream): its gradient joins here
+      if (dz_add != nullptr) add4(o, ld4<T>(dz_add + (size_t)row * H + col));
       if (dz_out != nullptr) st4<T>(dz_out + (size_t)row * H + col, o);
-      if (drop_p > 0.f) o = ln_bwd_chunk_drop(o, (uint32_t)row * H + col, drop_key, drop_thr, keep_scale);
+      if (drop_p > 0.f) o = bb_drop4(o, (uint32_t)row * H + col, drop_key, drop_thr, keep_scale);
       if (dx_out != nullptr) st4<T>(dx_out + (size_t)row * H + col, o);
-      ax[i].x += o.x; ax[i].y += o.y; ax[i].z += o.z; ax[i].w += o.w;
+      add4(ax[i], o);
     }
   }
   ln_bwd_store_partials<NV>(s_red, ag, ab, ax, partials, lane, wave);
@@ -288,25 +261,12 @@ __global__ __launch_bounds__(256) void ln_res32_fwd_kernel(const bf16_raw* __res
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int col = (i * 64 + lane) * 4;
-    float4 a = ld4<bf16_raw>(x + (size_t)row * H + col);
-    if (bias != nullptr) {
-      const float4 bb = *reinterpret_cast<const float4*>(bias + col);
-      a.x += bb.x; a.y += bb.y; a.z += bb.z; a.w += bb.w;
-    }
-    if (drop_p > 0.f) {
-      const uint32_t pr = ((uint32_t)row * H + col) >> 1;
-      const uint32_t b0 = bb_pair_bits(drop_key, pr), b1 = bb_pair_bits(drop_key, pr + 1);
-      a.x = bb_keep_lo(b0, drop_thr) ? a.x * keep_scale : 0.f;
-      a.y = bb_keep_hi(b0, drop_thr) ? a.y * keep_scale : 0.f;
-      a.z = bb_keep_lo(b1, drop_thr) ? a.z * keep_scale : 0.f;
-      a.w = bb_keep_hi(b1, drop_thr) ? a.w * keep_scale : 0.f;
-    }
-    if (residual != nullptr) {
-      const float4 r = ld4<TR>(residual + (size_t)row * H + col);
-      a.x += r.x; a.y += r.y; a.z += r.z; a.w += r.w;
-    }
-    v[i] = a;
+    const float4 a = ld4<bf16_raw>(x + (size_t)row * H + col);
+    const bool has_res = residual != nullptr;
+    const float4 r = has_res ? ld4<TR>(residual + (size_t)row * H + col) : make_float4(0.f, 0.f, 0.f, 0.f);
+    v[i] = ln_fwd_input(a, bias, col, drop_p, (uint32_t)row * H + col, drop_key, drop_thr, keep_scale, has_res, r);
   }
+  // ln_row_stats written out, for the reason given in ln_fwd_kernel
   float s = 0.f;
 #pragma unroll
   for (int i = 0; i < NV; ++i) s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
@@ -326,15 +286,44 @@ __global__ __launch_bounds__(256) void ln_res32_fwd_kernel(const bf16_raw* __res
   for (int i = 0; i < NV; ++i) {
     const int col = (i * 64 + lane) * 4;
     if (z_out != nullptr) st4<float>(z_out + (size_t)row * H + col, v[i]);
-    const float4 g = *reinterpret_cast<const float4*>(gamma + col);
-    const float4 b = *reinterpret_cast<const float4*>(beta + col);
-    float4 o;
-    o.x = (v[i].x - mean) * rstd * g.x + b.x;
-    o.y = (v[i].y - mean) * rstd * g.y + b.y;
-    o.z = (v[i].z - mean) * rstd * g.z + b.z;
-    o.w = (v[i].w - mean) * rstd * g.w + b.w;
+    const float4 o = ln_norm4(v[i], mean, rstd, gamma, beta, col);
     st4<bf16_raw>(y16 + (size_t)row * H + col, o);
     if (y32 != nullptr) st4<float>(y32 + (size_t)row * H + col, o);
+  }
+}
+
+// One row of the backward, shared by ln_res32_bwd_kernel and its load-ahead form.  d_of(i) / z_of(i) hand over chunk i of
+// d = dy16 + dy32 and of z: from memory in the one, from the prefetched LnRes32BwdRow in the other.  Callables, not two
+// filled arrays: the reduce of a chunk stays next to its operands; with the row gathered first the compiler contracts the
+// terms of s2 the other way round (which product goes into the fma) and dz differs in the last bit.
+// dz_bf16: dz_out is a bf16 tensor (the residual was a bf16 tensor -- where an fp32 residual stream starts).
+template <int NV, typename D, typename Z>
+__device__ __forceinline__ void ln_res32_bwd_row(int row, int lane, D&& d_of, Z&& z_of, float mu, float rs,
+                                                 const float4 (&g)[NV], float4 (&ag)[NV], float4 (&ab)[NV], float4 (&ax)[NV],
+                                                 float* __restrict__ dz_out, bf16_raw* __restrict__ dx_out, int dz_bf16,
+                                                 float drop_p, uint32_t drop_key, uint32_t drop_thr, float keep_scale) {
+  constexpr int H = NV * 256;
+  float4 d[NV], xh[NV];
+  float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    d[i] = d_of(i);
+    const float4 zz = z_of(i);
+    ln_bwd_chunk_reduce(d[i], zz, mu, rs, g[i], xh[i], ag[i], ab[i], s1, s2);
+  }
+  s1 = wave_sum(s1) * (1.0f / H);
+  s2 = wave_sum(s2) * (1.0f / H);
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int col = (i * 64 + lane) * 4;
+    float4 o = ln_bwd_chunk_dz(d[i], xh[i], rs, s1, s2);
+    if (dz_out != nullptr) {
+      if (dz_bf16) st4<bf16_raw>(reinterpret_cast<bf16_raw*>(dz_out) + (size_t)row * H + col, o);
+      else st4<float>(dz_out + (size_t)row * H + col, o);
+    }
+    if (drop_p > 0.f) o = bb_drop4(o, (uint32_t)row * H + col, drop_key, drop_thr, keep_scale);
+    if (dx_out != nullptr) st4<bf16_raw>(dx_out + (size_t)row * H + col, o);
+    add4(ax[i], o);
   }
 }
 
@@ -346,7 +335,6 @@ __global__ __launch_bounds__(256) void ln_res32_bwd_kernel(const bf16_raw* __res
                                                            float* __restrict__ partials, int rows, float drop_p,
                                                            uint32_t drop_thr, uint32_t drop_key,
                                                            const uint32_t* __restrict__ salt, int dz_bf16) {
-  // dz_bf16: dz_out is a bf16 tensor (the residual was a bf16 tensor -- where an fp32 residual stream starts)
   constexpr int H = NV * 256;
   if (drop_p > 0.f) drop_key = bb_salted(drop_key, salt);
   __shared__ float4 s_red[3][4][NV * 64];
@@ -361,34 +349,16 @@ __global__ __launch_bounds__(256) void ln_res32_bwd_kernel(const bf16_raw* __res
   }
   for (int row = blockIdx.x * 4 + wave; row < rows; row += gridDim.x * 4) {
     const float mu = mean[row], rs = rstd[row];
-    float4 d[NV], xh[NV];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int col = (i * 64 + lane) * 4;
-      d[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (dy16 != nullptr) d[i] = ld4<bf16_raw>(dy16 + (size_t)row * H + col);
-      if (dy32 != nullptr) {
-        const float4 e = ld4<float>(dy32 + (size_t)row * H + col);
-        d[i].x += e.x; d[i].y += e.y; d[i].z += e.z; d[i].w += e.w;
-      }
-      const float4 zz = ld4<float>(z + (size_t)row * H + col);
-      ln_bwd_chunk_reduce(d[i], zz, mu, rs, g[i], xh[i], ag[i], ab[i], s1, s2);
-    }
-    s1 = wave_sum(s1) * (1.0f / H);
-    s2 = wave_sum(s2) * (1.0f / H);
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int col = (i * 64 + lane) * 4;
-      float4 o = ln_bwd_chunk_dz(d[i], xh[i], rs, s1, s2);
-      if (dz_out != nullptr) {
-        if (dz_bf16) st4<bf16_raw>(reinterpret_cast<bf16_raw*>(dz_out) + (size_t)row * H + col, o);
-        else st4<float>(dz_out + (size_t)row * H + col, o);
-      }
-      if (drop_p > 0.f) o = ln_bwd_chunk_drop(o, (uint32_t)row * H + col, drop_key, drop_thr, keep_scale);
-      if (dx_out != nullptr) st4<bf16_raw>(dx_out + (size_t)row * H + col, o);
-      ax[i].x += o.x; ax[i].y += o.y; ax[i].z += o.z; ax[i].w += o.w;
-    }
+    auto d_of = [&](int i) __attribute__((always_inline)) {
+      const size_t at = (size_t)row * H + (i * 64 + lane) * 4;
+      float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (dy16 != nullptr) d = ld4<bf16_raw>(dy16 + at);
+      if (dy32 != nullptr) add4(d, ld4<float>(dy32 + at));
+      return d;
+    };
+    auto z_of = [&](int i) __attribute__((always_inline)) { return ld4<float>(z + (size_t)row * H + (i * 64 + lane) * 4); };
+    ln_res32_bwd_row<NV>(row, lane, d_of, z_of, mu, rs, g, ag, ab, ax, dz_out, dx_out, dz_bf16, drop_p, drop_key, drop_thr,
+                         keep_scale);
   }
   ln_bwd_store_partials<NV>(s_red, ag, ab, ax, partials, lane, wave);
 }
@@ -396,8 +366,8 @@ __global__ __launch_bounds__(256) void ln_res32_bwd_kernel(const bf16_raw* __res
 // The same with the NEXT row's loads in flight.  Up to 512 workgroups (5 120 rows) a launch has two waves per SIMD and a
 // wave two or three rows, each a dependent load -> reduce -> store chain: the kernel is latency-bound and the registers for
 // a second row are free.  The host picks this form there (ln_res32_bwd_loads_ahead); larger launches need four waves per
-// SIMD (<= 128 VGPRs) and keep the kernel above.  Which rows a wave takes, the order in which it adds them into its column
-// partials and the arithmetic of a row (ln_bwd_chunk_*) are those of the kernel above.
+// SIMD (<= 128 VGPRs) and keep the kernel above.  Which rows a wave takes and the order in which it adds them into its
+// column partials are those of the kernel above; the arithmetic of a row is the same function (ln_res32_bwd_row).
 template <int NV> struct LnRes32BwdRow {
   uint2 d16[NV];          // dy16, packed (when there is one)
   float4 d32[NV], z[NV];  // dy32 (when there is one), z
@@ -411,7 +381,6 @@ __global__ __launch_bounds__(256) void ln_res32_bwd_ahead_kernel(const bf16_raw*
                                                                  float* __restrict__ partials, int rows, float drop_p,
                                                                  uint32_t drop_thr, uint32_t drop_key,
                                                                  const uint32_t* __restrict__ salt, int dz_bf16) {
-  // dz_bf16: dz_out is a bf16 tensor (the residual was a bf16 tensor -- where an fp32 residual stream starts)
   constexpr int H = NV * 256;
   if (drop_p > 0.f) drop_key = bb_salted(drop_key, salt);
   __shared__ float4 s_red[3][4][NV * 64];
@@ -436,34 +405,15 @@ __global__ __launch_bounds__(256) void ln_res32_bwd_ahead_kernel(const bf16_raw*
     }
   };
   auto apply = [&](int row, const LnRes32BwdRow<NV>& r) __attribute__((always_inline)) {
-    const float mu = r.mu, rs = r.rs;
-    float4 d[NV], xh[NV];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      d[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (dy16 != nullptr) d[i] = raw4<bf16_raw>::f32(r.d16[i]);
-      if (dy32 != nullptr) {
-        const float4 e = r.d32[i];
-        d[i].x += e.x; d[i].y += e.y; d[i].z += e.z; d[i].w += e.w;
-      }
-      const float4 zz = r.z[i];
-      ln_bwd_chunk_reduce(d[i], zz, mu, rs, g[i], xh[i], ag[i], ab[i], s1, s2);
-    }
-    s1 = wave_sum(s1) * (1.0f / H);
-    s2 = wave_sum(s2) * (1.0f / H);
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int col = (i * 64 + lane) * 4;
-      float4 o = ln_bwd_chunk_dz(d[i], xh[i], rs, s1, s2);
-      if (dz_out != nullptr) {
-        if (dz_bf16) st4<bf16_raw>(reinterpret_cast<bf16_raw*>(dz_out) + (size_t)row * H + col, o);
-        else st4<float>(dz_out + (size_t)row * H + col, o);
-      }
-      if (drop_p > 0.f) o = ln_bwd_chunk_drop(o, (uint32_t)row * H + col, drop_key, drop_thr, keep_scale);
-      if (dx_out != nullptr) st4<bf16_raw>(dx_out + (size_t)row * H + col, o);
-      ax[i].x += o.x; ax[i].y += o.y; ax[i].z += o.z; ax[i].w += o.w;
-    }
+    auto d_of = [&](int i) __attribute__((always_inline)) {
+      float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (dy16 != nullptr) d = raw4<bf16_raw>::f32(r.d16[i]);
+      if (dy32 != nullptr) add4(d, r.d32[i]);
+      return d;
+    };
+    auto z_of = [&](int i) __attribute__((always_inline)) { return r.z[i]; };
+    ln_res32_bwd_row<NV>(row, lane, d_of, z_of, r.mu, r.rs, g, ag, ab, ax, dz_out, dx_out, dz_bf16, drop_p, drop_key, drop_thr,
+                         keep_scale);
   };
   walk_rows_ahead<LnRes32BwdRow<NV>>(blockIdx.x * 4 + wave, rows, gridDim.x * 4, fill, apply);
   ln_bwd_store_partials<NV>(s_red, ag, ab, ax, partials, lane, wave);
@@ -672,7 +622,7 @@ __global__ __launch_bounds__(256) void colwise_bwd_kernel(const T* __restrict__ 
         d[k] = act_grad4_of<T, MODE == 2 ? 1 : 0>(d[k], a[k], b);
         st4<T>(dx + (size_t)(r + k) * C + c0, d[k]);
       }
-      acc.x += d[k].x; acc.y += d[k].y; acc.z += d[k].z; acc.w += d[k].w;
+      add4(acc, d[k]);
     }
   }
   for (; r < rows; ++r) {
@@ -682,7 +632,7 @@ __global__ __launch_bounds__(256) void colwise_bwd_kernel(const T* __restrict__ 
       d = act_grad4_of<T, MODE == 2 ? 1 : 0>(d, a, b);
       st4<T>(dx + (size_t)r * C + c0, d);
     }
-    acc.x += d.x; acc.y += d.y; acc.z += d.z; acc.w += d.w;
+    add4(acc, d);
   }
   *reinterpret_cast<float4*>(partials + (size_t)blockIdx.x * C + c0) = acc;
 }
@@ -743,18 +693,14 @@ __device__ __forceinline__ void accum_fold(const T* part_, float* sink_, size_t 
 #pragma unroll
       for (int k = 0; k < ACCUM_SC; ++k)
 #pragma unroll
-        for (int u = 0; u < ACCUM_U; ++u) {
-          acc[u].x += v[k][u].x; acc[u].y += v[k][u].y; acc[u].z += v[k][u].z; acc[u].w += v[k][u].w;
-        }
+        for (int u = 0; u < ACCUM_U; ++u) add4(acc[u], v[k][u]);
     }
     for (; s < S; ++s) {
       float4 v[ACCUM_U];
 #pragma unroll
       for (int u = 0; u < ACCUM_U; ++u) v[u] = gld4<T>(part + ((size_t)s * stride4 + idx[u]) * 4);
 #pragma unroll
-      for (int u = 0; u < ACCUM_U; ++u) {
-        acc[u].x += v[u].x; acc[u].y += v[u].y; acc[u].z += v[u].z; acc[u].w += v[u].w;
-      }
+      for (int u = 0; u < ACCUM_U; ++u) add4(acc[u], v[u]);
     }
 #pragma unroll
     for (int u = 0; u < ACCUM_U; ++u)
@@ -840,10 +786,7 @@ __global__ __launch_bounds__(256) void embedding_grad_kernel(const int64_t* __re
 #pragma unroll
         for (int j = 0; j < EG_MAXJ; ++j) {
           const int c = (lane + 64 * j) * 4;
-          if (c < H) {
-            const float4 v = ld4<T>(d + (size_t)row * H + c);
-            acc[j].x += v.x; acc[j].y += v.y; acc[j].z += v.z; acc[j].w += v.w;
-          }
+          if (c < H) add4(acc[j], ld4<T>(d + (size_t)row * H + c));
         }
       }
     }
@@ -894,7 +837,7 @@ __global__ __launch_bounds__(256) void embedding_grad_sliced_kernel(const int64_
         if (r + j < r1 && ids[r + j] == t) v[j] = ld4<T>(d + (size_t)(r + j) * H + c);
       }
 #pragma unroll
-      for (int j = 0; j < 4; ++j) { acc.x += v[j].x; acc.y += v[j].y; acc.z += v[j].z; acc.w += v[j].w; }
+      for (int j = 0; j < 4; ++j) add4(acc, v[j]);
     }
     *reinterpret_cast<float4*>(partials + ((size_t)s * ntab + t) * H + c) = acc;
   }
@@ -1002,17 +945,8 @@ __global__ __launch_bounds__(256) void dropout_add_kernel(const TI* __restrict__
                                                           uint32_t thr, uint32_t key, const uint32_t* __restrict__ salt) {
   key = bb_salted(key, salt);
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-    float4 a = ld4<TI>(x + i * 4);
-    const uint32_t pr = (uint32_t)(i * 2);
-    const uint32_t b0 = bb_pair_bits(key, pr), b1 = bb_pair_bits(key, pr + 1);
-    a.x = bb_keep_lo(b0, thr) ? a.x * keep_scale : 0.f;
-    a.y = bb_keep_hi(b0, thr) ? a.y * keep_scale : 0.f;
-    a.z = bb_keep_lo(b1, thr) ? a.z * keep_scale : 0.f;
-    a.w = bb_keep_hi(b1, thr) ? a.w * keep_scale : 0.f;
-    if (residual != nullptr) {
-      const float4 r = ld4<TO>(residual + i * 4);
-      a.x += r.x; a.y += r.y; a.z += r.z; a.w += r.w;
-    }
+    float4 a = bb_drop4(ld4<TI>(x + i * 4), (uint32_t)(i * 4), key, thr, keep_scale);   // n < 2^32 (checked by the entry)
+    if (residual != nullptr) add4(a, ld4<TO>(residual + i * 4));
     st4<TO>(y + i * 4, a);
   }
 }

@@ -9,7 +9,8 @@
 //
 // Layout as in rowops.hip: activations are (rows, H) row-major with H % 256 == 0 and H <= 1024; one 64-lane wave owns one
 // row and keeps it in registers (H / 64 values per lane as float4s).  The residual stream z32 is fp32 whatever the compute
-// dtype T of the GEMM operands; statistics are fp32.  No atomics, plain vector stores, one launch per entry.
+// dtype T of the GEMM operands; statistics are fp32, and every LayerNorm here is ln_row_stats + ln_norm4 (common.h), the
+// row body of ln_fwd_kernel.  No atomics, plain vector stores, one launch per entry.
 #include <math.h>
 
 #include "common.h"
@@ -55,32 +56,6 @@ __global__ __launch_bounds__(256) void vit_patchify_kernel(const uint8_t* __rest
 }
 
 // =============================================================================================
-// LayerNorm of a row held in registers, as ln_fwd_kernel computes it (two-pass variance, eps inside the square root)
-// =============================================================================================
-template <int NV>
-__device__ __forceinline__ void vit_row_stats(const float4 (&v)[NV], float eps, float& mean, float& rstd) {
-  constexpr int H = NV * 256;
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < NV; ++i) s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-  mean = wave_sum(s) * (1.0f / H);
-  float q = 0.f;
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const float dx = v[i].x - mean, dy = v[i].y - mean, dz = v[i].z - mean, dw = v[i].w - mean;
-    q += (dx * dx + dy * dy) + (dz * dz + dw * dw);
-  }
-  rstd = rsqrtf(wave_sum(q) * (1.0f / H) + eps);
-}
-__device__ __forceinline__ float4 vit_norm4(float4 v, float mean, float rstd, const float* __restrict__ gamma,
-                                            const float* __restrict__ beta, int col) {
-  const float4 g = *reinterpret_cast<const float4*>(gamma + col);
-  const float4 b = *reinterpret_cast<const float4*>(beta + col);
-  return make_float4((v.x - mean) * rstd * g.x + b.x, (v.y - mean) * rstd * g.y + b.y, (v.z - mean) * rstd * g.z + b.z,
-                     (v.w - mean) * rstd * g.w + b.w);
-}
-
-// =============================================================================================
 // embed_prenorm: token row t of image n is class_embedding + pos[0] (t = 0) or conv_out[n, t - 1] + pos[t]; z32 = ln_pre
 // of it (the start of the residual stream), y = ln_1 of block 0 on z32.  The row stays in registers between the two.
 // =============================================================================================
@@ -105,18 +80,18 @@ __global__ __launch_bounds__(256) void vit_embed_prenorm_kernel(const T* __restr
     v[i] = make_float4(a.x + p.x, a.y + p.y, a.z + p.z, a.w + p.w);
   }
   float mean, rstd;
-  vit_row_stats<NV>(v, eps, mean, rstd);
+  ln_row_stats<NV>(v, eps, mean, rstd);
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int col = (i * 64 + lane) * 4;
-    v[i] = vit_norm4(v[i], mean, rstd, g_pre, b_pre, col);
+    v[i] = ln_norm4(v[i], mean, rstd, g_pre, b_pre, col);
     st4<float>(z32 + (size_t)row * H + col, v[i]);
   }
-  vit_row_stats<NV>(v, eps, mean, rstd);
+  ln_row_stats<NV>(v, eps, mean, rstd);
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int col = (i * 64 + lane) * 4;
-    st4<T>(y + (size_t)row * H + col, vit_norm4(v[i], mean, rstd, g1, b1, col));
+    st4<T>(y + (size_t)row * H + col, ln_norm4(v[i], mean, rstd, g1, b1, col));
   }
 }
 
@@ -155,20 +130,20 @@ __global__ __launch_bounds__(256) void vit_bias_residual_prenorm_kernel(float* _
       return;
     }
     float mean, rstd;
-    vit_row_stats<NV>(v, eps, mean, rstd);
+    ln_row_stats<NV>(v, eps, mean, rstd);
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const int col = (i * 64 + lane) * 4;
-      st4<T>(y + (size_t)n * H + col, vit_norm4(v[i], mean, rstd, gamma, beta, col));
+      st4<T>(y + (size_t)n * H + col, ln_norm4(v[i], mean, rstd, gamma, beta, col));
     }
   } else {
     float mean, rstd;
-    vit_row_stats<NV>(v, eps, mean, rstd);
+    ln_row_stats<NV>(v, eps, mean, rstd);
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const int col = (i * 64 + lane) * 4;
       st4<float>(z32 + (size_t)row * H + col, v[i]);
-      st4<T>(y + (size_t)row * H + col, vit_norm4(v[i], mean, rstd, gamma, beta, col));
+      st4<T>(y + (size_t)row * H + col, ln_norm4(v[i], mean, rstd, gamma, beta, col));
     }
   }
 }
