@@ -477,7 +477,9 @@ int bevbert_nav_expert(const double* dist, const int16_t* pred, int N, int S, co
 
 /* One navigation step's decision for B samples from logits (B,C) (dtype 0/1, -inf = masked).  feedback 0 = teacher
  * (targets), 1 = argmax, 2 = sample (inverse CDF of a uniform draw), 3 = expl_sample (first max of the logits = of the probabilities; with
- * probability P(u > expl_max_ratio) a uniform pick among masks (B,C) u8).  Draws hash (seed, t) with the step salt.
+ * probability P(u > expl_max_ratio) a uniform pick among masks (B,C) u8).  Draws (since 0.2.3 in a domain of their own):
+ * k = salted(hash(site_key(seed, t) ^ BB_STREAM_NAV)), u0 = 24 bits of hash(k ^ 4 b) (sample; explore or not),
+ * u1 = 24 bits of hash(k ^ (4 b + 1)) (which mask slot); salted(x) = hash(x ^ step salt), see csrc/common.h.
  * Live samples store p[0] as the stop score of node cur in stop_scores (B,N) (first-insertion order in stop_order (B,N),
  * n_stop (B)).  Stop: teacher / sample at goal[b], else a == 0; also ended, no_vp_left (may be NULL), t == max_len - 1.
  * Outputs: a_t (B) i64, node (B) = cand[b, a], or -1 when the sample does not move (the reference's None action);
@@ -537,8 +539,9 @@ int bevbert_wp_ring_attn(const void* qkv, void* out, int B, int nh, float scale,
  * one wrap row on either side; 5 rounds of arg-max (first index wins ties) + suppression, sigma = (7, 5); the surviving
  * picks of rows 1..120 in row-major order are the candidates: cand_count (B).  in_train != 0 (waypoint_aug): candidate k
  * is replaced by an inverse-CDF draw over the 120 cells of its image's region, region_probs (B,5,120) (0 for k >=
- * cand_count), with the uniform rand (B,5) = 24 bits of hash((seed, t), step salt, 8 b + k) -- all five are written, the
- * first cand_count are used.  Outputs, padding -1 / 0: cand_angle_idx, cand_dist_idx, cand_img_idx (counter-clockwise)
+ * cand_count), with the uniform rand (B,5) = 24 bits of hash(key ^ (8 b + k)), key = salted(hash(site_key(seed, t) ^
+ * BB_STREAM_WAYPOINT)) (csrc/common.h; a domain of its own since 0.2.3) -- all five are written, the first cand_count
+ * are used.  Outputs, padding -1 / 0: cand_angle_idx, cand_dist_idx, cand_img_idx (counter-clockwise)
  * (B,5) i32; cand_angle_fts (B,5,4) = [sin, cos, 0, 1] of the clockwise angle; cand_angles (B,5) counter-clockwise
  * radians; cand_distances (B,5) = (dist_idx + 1) / 4.  region_probs and rand may be NULL when in_train == 0. */
 int bevbert_wp_candidates(const float* logits, int B, int in_train, uint32_t seed, int t, int* cand_count,
@@ -599,7 +602,10 @@ typedef struct bevbert_ce_state {
  * candidate j < cand_count[b] (cand_angles / cand_distances (B,C) f32, C <= 16, as bevbert_wp_candidates writes them)
  * localized to a node or created as / merged into a ghost with the j-th row of pano (B,L,H) whose nav_types (B,L) i64 is 1;
  * avg_pano (B,H) becomes the node embedding (dtype of the state).  ghost_aug a > 0: every live ghost's augmented position
- * is redrawn as mean + clip(N(0, (a, 0, a)), +-a), a pure function of (seed, step salt, step_id, b, ghost id).  Then
+ * is redrawn as mean + clip(N(0, (a, 0, a)), +-a), a pure function of (seed, step salt, step_id, b, ghost id): key =
+ * salted(hash(hash(seed ^ 0x9e3779b9) ^ BB_STREAM_GHOST)) (csrc/common.h; a domain of its own since 0.2.3), kb =
+ * hash(hash(key ^ step_id) ^ b), kg = hash(kb ^ g), u1 = (24 bits of hash(kg ^ 1) + 1) / 2^24, u2 = 24 bits of
+ * hash(kg ^ 2) / 2^24, Box-Muller in double.  Then
  * all-pairs Dijkstra.  cand_slot (B,C): the id a candidate went to, -1 = padding / refused (a candidate
  * without a nav_types == 1 row is refused with the overflow flag). */
 int bevbert_ce_update(const bevbert_ce_state* st, const double* pose, const uint8_t* live, const int* step_id,

@@ -37,7 +37,7 @@ BEVBERT_API int bevbert_zero(void* p, int64_t bytes, hipStream_t stream) {
   return BB_OK;
 }
 
-BEVBERT_API int bevbert_version(void) { return 202; }  // 0.2.2: the bevbert_ce_* entry points (csrc/ce_map.hip)
+BEVBERT_API int bevbert_version(void) { return 203; }  // 0.2.3: domain-separated keys of the nav / waypoint / ghost draws
 
 static const uint32_t* g_step_salt = nullptr;
 const uint32_t* bb_step_salt() { return g_step_salt; }

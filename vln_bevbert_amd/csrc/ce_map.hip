@@ -331,7 +331,7 @@ BEVBERT_API int bevbert_ce_update(const bevbert_ce_state* st, const double* pose
                  cand_slot, "ce_update: null tensor%s", "");
   hipLaunchKernelGGL(ce_update_kernel, dim3(st->B), dim3(256), 0, stream, *st, pose, live, step_id, cand_count,
                      cand_angles, cand_distances, C, avg_pano, pano, nav_types, L, loc_noise, ghost_aug,
-                     bb_hash32(seed ^ 0x9e3779b9u), bb_step_salt(), cand_slot);
+                     bb_stream_key(bb_hash32(seed ^ 0x9e3779b9u), BB_STREAM_GHOST), bb_step_salt(), cand_slot);
   BB_CHECK_LAUNCH("ce_update");
   return BB_OK;
 }

@@ -318,8 +318,8 @@ BEVBERT_API int bevbert_nav_action(const void* logits, int dtype, int B, int C, 
   if (B <= 0) return BB_OK;
   hipLaunchKernelGGL(ne_action_kernel, dim3(B), dim3(64), 0, stream, logits, dtype == BB_BF16, C, feedback, t, max_len,
                      targets, cand, cur, goal, ended, no_vp_left, masks, stop_scores, stop_order, n_stop, N,
-                     expl_max_ratio, bb_site_key(seed, (uint64_t)t), bb_step_salt(), a_t, node, just_ended, stop_node,
-                     entropy, rand);
+                     expl_max_ratio, bb_stream_key(bb_site_key(seed, (uint64_t)t), BB_STREAM_NAV), bb_step_salt(), a_t,
+                     node, just_ended, stop_node, entropy, rand);
   BB_CHECK_LAUNCH("nav_action");
   return BB_OK;
 }

@@ -267,9 +267,10 @@ BEVBERT_API int bevbert_wp_candidates(const float* logits, int B, int in_train, 
   BB_REQUIRE(logits && cand_count && cand_angle_idx && cand_dist_idx && cand_img_idx && cand_angle_fts && cand_angles &&
                  cand_distances && heat, "wp_candidates: null tensor%s", "");
   BB_REQUIRE(!in_train || (region_probs && rand), "wp_candidates: the training draw needs region_probs and rand%s", "");
-  hipLaunchKernelGGL(wp_candidates_kernel, dim3(B), dim3(256), 0, stream, logits, in_train, bb_site_key(seed, (uint64_t)t),
-                     bb_step_salt(), cand_count, cand_angle_idx, cand_dist_idx, cand_img_idx, cand_angle_fts, cand_angles,
-                     cand_distances, region_probs, heat, rand);
+  hipLaunchKernelGGL(wp_candidates_kernel, dim3(B), dim3(256), 0, stream, logits, in_train,
+                     bb_stream_key(bb_site_key(seed, (uint64_t)t), BB_STREAM_WAYPOINT), bb_step_salt(), cand_count,
+                     cand_angle_idx, cand_dist_idx, cand_img_idx, cand_angle_fts, cand_angles, cand_distances,
+                     region_probs, heat, rand);
   BB_CHECK_LAUNCH("wp_candidates");
   return BB_OK;
 }

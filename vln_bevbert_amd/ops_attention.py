@@ -58,6 +58,9 @@ class _Attention(torch.autograd.Function):
         o = torch.empty(B, Lq, H, dtype=q.dtype, device=q.device)
         need_grad = any(ctx.needs_input_grad)
         lse = torch.empty(B, nh, Lq, dtype=torch.float32, device=q.device) if need_grad else None
+        # The kernels index B * nh * Lq * Lk2 elements (Lk2 = Lk rounded up to even, attn_common.h), more than the
+        # B * nh * Lq * Lk reserved here for odd Lk.  Harmless: (seed, offset) is hashed into the site's key and the
+        # element index is XORed into it, so what separates two sites is that their offsets differ, not how far apart.
         off = RT.next_offset(B * nh * Lq * Lk) if drop_p > 0 else 0
         scale = 1.0 / math.sqrt(HEAD_DIM)
         if key_mask is not None:

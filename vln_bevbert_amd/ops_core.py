@@ -29,8 +29,10 @@ class _Runtime:
     """Dropout stream + scratch buffers.
 
     A dropout site's mask is a pure function of (seed, offset, step salt, element index).  ``seed`` is fixed for the
-    life of the process and ``offset`` advances by the element count of every dropout site, so each site draws from a
-    disjoint counter range -- both are launch ARGUMENTS and freeze into a captured hipGraph.  What changes from step to
+    life of the process and ``offset`` advances by the element count of every dropout site, so the sites of a step have
+    distinct offsets and hence distinct keys.  (The counter ranges are NOT disjoint: (seed, offset) is hashed into a
+    32-bit key and the element pair index is XORed into it, so every site is an XOR-shifted window into one 2^32-entry
+    table -- csrc/common.h.)  Both are launch ARGUMENTS and freeze into a captured hipGraph.  What changes from step to
     step is the salt: one 32-bit word in device memory (registered with the library through bevbert_set_step_salt)
     that ``new_step`` rewrites with a 4-byte fill on the stream; a replayed graph therefore draws fresh masks."""
 
