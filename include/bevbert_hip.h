@@ -688,6 +688,41 @@ int bevbert_vit_bias_quickgelu(const void* x, const float* bias, void* y, int ro
 int bevbert_depth_grid_pool(const float* depth, const int* view_map, float* out, int N, int n_src, int Hd, int Wd, int G,
                             hipStream_t stream);
 
+/* ---- depth ResNet encoder (csrc/depth_resnet.hip, depth_resnet.py): forward-only kernels around the library GEMMs ------
+ * Activations are NHWC; `dtype` is the compute dtype of the GEMM operands (BB_F32 or BB_BF16).  A GroupNorm shape (C, G)
+ * is supported when C is a power of two in [4, 1024], G a power of two up to 16 and C / G is 2 or a multiple of 4.  No
+ * atomics: two calls on the same input give the same bits. */
+
+/* avg_pool2d(2) + Conv2d(1, 32, 7, stride 2, pad 3, no bias), fp32: depth (n_src, H, W) -> out (N, H / 4, W / 4, 32), raw
+ * (not normalised); H and W multiples of 4; weight_t (49, 32): the convolution weight (32, 1, 7, 7) transposed to
+ * (ky * 7 + kx, c); view_map as in bevbert_vit_patchify. */
+int bevbert_dr_stem(const float* depth, const int* view_map, const float* weight_t, float* out, int N, int n_src, int H, int W,
+                    hipStream_t stream);
+
+/* GroupNorm statistics of x (N, HW, C) dtype (BB_F32 is always accepted): mean, rstd (N, G) f32, rstd = 1 / sqrt(var + eps)
+ * with the biased variance, computed from squared distances to the mean (never E[x^2] - mean^2).  An image is cut into
+ * ceil(HW / (8192 / C)) chunks; with more than one chunk `partial` must hold N * chunks * G * 2 floats. */
+int bevbert_dr_gn_stats(const void* x, float* partial, int64_t partial_floats, float* mean, float* rstd, int N, int HW, int C,
+                        int G, float eps, int dtype, hipStream_t stream);
+
+/* y = relu(gn(x) [+ second term]) over (N, HW, C) dtype with gn(x) = (x - mean[n, g]) * rstd[n, g] * gamma[c] + beta[c]:
+ * mode 0 nothing added; mode 1 + r (N, HW, C) dtype; mode 2 + gn2(r) with mean2, rstd2, gamma2, beta2 (the downsample
+ * branch); mode 3 as mode 0 but y is written (N, C, HW).  Unused pointers may be NULL.  y may be x or r except in mode 3. */
+int bevbert_dr_gn_apply(const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                        const void* r, const float* mean2, const float* rstd2, const float* gamma2, const float* beta2, void* y,
+                        int N, int HW, int C, int G, int mode, int dtype, hipStream_t stream);
+
+/* The stem's form: x (N, H, W, C) f32 raw -> y (N, ceil(H / 2), ceil(W / 2), C) dtype = relu(MaxPool2d(3, 2, 1)(gn(x))); the
+ * maximum is taken over the normalised values. */
+int bevbert_dr_gn_relu_maxpool(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                               void* y, int N, int H, int W, int C, int G, int dtype, hipStream_t stream);
+
+/* Rows of a ksize x ksize convolution (ksize 1 or 3, padding (ksize - 1) / 2, stride 1 or 2) on x (N, H, W, C) dtype:
+ * out (N * Ho * Wo, ksize * ksize * C) with Ho = (H - 1) / stride + 1, column order (ky, kx, c), zeros outside the image.
+ * C * sizeof(dtype) must be a multiple of 16. */
+int bevbert_dr_gather_rows(const void* x, void* out, int N, int H, int W, int C, int ksize, int stride, int dtype,
+                           hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

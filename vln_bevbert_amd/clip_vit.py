@@ -14,7 +14,8 @@ in a hipGraph in front of waypoint_step / CEGraphMap:
 
 Arithmetic: the residual stream is fp32 (csrc/vit.hip), the GEMM and attention operands are in the compute dtype (fp32 or
 bf16); GEMMs go through ops.linear (hipBLASLt, cached plans), attention through ops.attention_self with batch = images.
-Not built: the depth ResNet encoder, CLIP's text tower, fp16 operands, any backward.
+The depth ResNet encoder is depth_resnet.py (encode_observations there runs both on one view map).
+Not built: CLIP's text tower, fp16 operands, any backward.
 """
 import ctypes
 

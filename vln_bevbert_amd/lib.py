@@ -19,7 +19,7 @@ CSRC = os.path.join(_HERE, "csrc")
 # instructions of the SIMD's other wave while plain ones do (scripts/probes/mfma_valu_overlap.hip,
 # profiles/r05_mfma_valu_overlap_probe.txt).  Measured on that kernel: no difference either way.
 EXTRA_FLAGS = {"attn_fwd4.hip": ["-fno-slp-vectorize"]}
-SOURCES = ["splat.hip", "rowops.hip", "attn_simple.hip", "attn_f32.hip", "attn_mfma.hip", "attn_bwd1.hip", "attn_fwd2.hip", "attn_fwd4.hip", "attn_bwd2.hip", "attn_bwd3.hip", "attn_small.hip", "attn_short.hip", "smallk.hip", "sap_loss.hip", "graph_nav.hip", "nav_expert.hip", "waypoint.hip", "ce_map.hip", "vit.hip", "gemm.hip", "capi.hip"]
+SOURCES = ["splat.hip", "rowops.hip", "attn_simple.hip", "attn_f32.hip", "attn_mfma.hip", "attn_bwd1.hip", "attn_fwd2.hip", "attn_fwd4.hip", "attn_bwd2.hip", "attn_bwd3.hip", "attn_small.hip", "attn_short.hip", "smallk.hip", "sap_loss.hip", "graph_nav.hip", "nav_expert.hip", "waypoint.hip", "ce_map.hip", "vit.hip", "depth_resnet.hip", "gemm.hip", "capi.hip"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "bevbert_hip.h")
 
 F32, BF16, F16 = 0, 1, 2
@@ -159,6 +159,11 @@ _PROTOS = {
     "bevbert_vit_bias_residual_prenorm": [_P] * 7 + [_I, _I, _I, _F, _I, _I, _P],
     "bevbert_vit_bias_quickgelu": [_P, _P, _P, _I, _I, _I, _P],
     "bevbert_depth_grid_pool": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "bevbert_dr_stem": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "bevbert_dr_gn_stats": [_P, _P, _I64, _P, _P, _I, _I, _I, _I, _F, _I, _P],
+    "bevbert_dr_gn_apply": [_P] * 11 + [_I, _I, _I, _I, _I, _I, _P],
+    "bevbert_dr_gn_relu_maxpool": [_P] * 6 + [_I, _I, _I, _I, _I, _I, _P],
+    "bevbert_dr_gather_rows": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
 }
 
 
