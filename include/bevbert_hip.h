@@ -654,6 +654,43 @@ int bevbert_ce_remember(const bevbert_ce_state* st, const uint8_t* live, const v
 int bevbert_ce_bev_select(const bevbert_ce_state* st, const uint8_t* live, int order, int R, int* rows, uint8_t* row_live,
                           hipStream_t stream);
 
+/* ---- Training through the ghost-node map (csrc/ce_train.hip, ce_train.py; since 0.2.4) -------------------------------
+ * The reference keeps the panorama embeddings as live tensors inside GraphMap (ss_trainer_BEV.py:1060-1066), so the loss of
+ * step t reaches the panorama encoder's pass of every step s <= t through _nav_gmap_variable.  The device map keeps them
+ * in raw arrays; these entries record what its updates did (the "tape") and run the adjoint of its embedding path.  A tape
+ * of T steps: cur (T,B) i32 the node a step made (-1: none), live (T,B) u8, slot / row (T,B,C) i32 the ghost id N + g a
+ * candidate went to and the row of pano it brought (-1 / -1: localised to a node, refused, padding), ids (T,B,G) i64 the
+ * gmap_ids of a step's listing, cnt (T,B,Gh) i32 the ghosts' g_npos at that listing, and the fp32 accumulators d_avg
+ * (T,B,H), d_pano (T,B,L,H).  No atomics, no host synchronisation. */
+
+/* After bevbert_ce_update of one step: fills that step's slices cur_out (B), live_out (B), slot_out / row_out (B,C) from the
+ * state's cur_vp (B), the live mask, the update's cand_slot (B,C) and nav_types (B,L) i64 (candidate j brings the j-th row
+ * whose type is 1).  last_cur (B) i32 is the tape's own memory of the node recorded last (-1 at the start of an episode):
+ * a live map whose cur_vp did not move (update refused at node capacity) is recorded as not live. */
+int bevbert_ce_tape_record(const int* cur_vp, const uint8_t* live, const int* cand_slot, const int64_t* nav_types, int B,
+                           int N, int C, int L, int* last_cur, int* cur_out, uint8_t* live_out, int* slot_out, int* row_out,
+                           hipStream_t stream);
+
+/* Adjoint of gmap_img_fts of tape step t (0 <= t < T) for every step s <= t, one launch: with dG (B,G,H) `dtype` (BB_F32 /
+ * BB_BF16) = d gmap_img_fts[t], for every map live at s and at t
+ *   d_avg[s][b, :]            += dG[b, 1 + e, :]                 e = cur[s][b], the node step s made;
+ *   d_pano[s][b, row, :]      += dG[b, r, :] / cnt[t][b, g]      for each candidate of step s with slot N + g whose ghost is
+ *                                                                 listed at row r of ids[t][b] (a consumed ghost is not).
+ * One wave per (s, b, avg | candidate): each reads at most one row of dG and adds into its own accumulator row, so the
+ * result does not depend on scheduling; a row receives the consumer steps in the order of the calls (backward: t
+ * descending).  H is any positive integer (16-byte loads when H % 4 == 0). */
+int bevbert_ce_embeds_bwd(const void* dG, int dtype, int t, int T, int B, int N, int Gh, int C, int L, int H, const int* cur,
+                          const uint8_t* live, const int* slot, const int* row, const int64_t* ids, const int* cnt,
+                          float* d_avg, float* d_pano, hipStream_t stream);
+
+/* The action draw of a training rollout (ss_trainer_BEV.py:1097-1100): a_t (B) i64 = the inverse-CDF sample of
+ * softmax(logits (B,C) f32 / bf16, -inf on masked slots) with the rule of bevbert_nav_action's `sample` mode (fp32 softmax,
+ * cumulative sum in row order, the first j with u0 < c and p > 0, else the last positive j), replaced by teacher[b] (i64,
+ * -100 passes through) where u1 <= sample_ratio.  u0 / u1 (B) f32 = 24 bits of hash(k ^ 4 b) / hash(k ^ (4 b + 1)) / 2^24,
+ * k = salted(hash(site_key(seed, t) ^ BB_STREAM_CE_ACTION)) (csrc/common.h). */
+int bevbert_ce_sample_action(const void* logits, int dtype, int B, int C, const int64_t* teacher, float sample_ratio,
+                             uint32_t seed, int t, int64_t* a_t, float* u0, float* u1, hipStream_t stream);
+
 /* ---- CLIP vision transformer (csrc/vit.hip, clip_vit.py): forward-only row kernels ------------------------------------
  * Rows are (rows, H) row-major, H in {256, 512, 768, 1024}; the residual stream z32 is fp32 whatever `dtype` (the
  * compute dtype of the GEMM operands: BB_F32 or BB_BF16). */

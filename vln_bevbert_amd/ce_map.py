@@ -177,7 +177,8 @@ class CEGraphMap:
         """identify_node + estimate_cand_pos + update_graph for every live map (graph_utils.py:182-262).  The candidate
         tensors are waypoint_step's own device outputs (cand_count (B) i32, cand_angles / cand_distances (B,C) f32),
         avg_pano_embeds (B,H) and pano_embeds (B,L,H) the panorama encoder's, nav_types (B,L) i64 the encoder's input:
-        candidate j takes the j-th row whose type is 1.  Embeddings enter as constants.  ``cur_pos`` / ``heading`` /
+        candidate j takes the j-th row whose type is 1.  Embeddings enter as constants (``ce_train.CEMapTape`` wraps this
+        call and ``nav_gmap_variable`` for training: it carries the gradient of ``gmap_img_fts`` back to them).  ``cur_pos`` / ``heading`` /
         ``live`` given: ``stage`` is called first with ``step_id``; otherwise the staged values are used as they are.  Returns cand_slot (B,C) i32: the id each candidate went to."""
         if cur_pos is not None:
             self.stage(step_id, cur_pos, heading, live)

@@ -187,6 +187,7 @@ __device__ __forceinline__ float4 ln_norm4(float4 v, float mean, float rstd, con
 //   nav action     k = salted(bb_stream_key(bb_site_key(seed, t), BB_STREAM_NAV))        counter = 4 b, 4 b + 1
 //   waypoint       k = salted(bb_stream_key(bb_site_key(seed, t), BB_STREAM_WAYPOINT))   counter = 8 b + candidate
 //   ghost noise    k = salted(bb_stream_key(hash(seed ^ 0x9e3779b9), BB_STREAM_GHOST))   then the chain in ce_update_kernel
+//   CE action      k = salted(bb_stream_key(bb_site_key(seed, t), BB_STREAM_CE_ACTION))  counter = 4 b, 4 b + 1
 // The domain constants keep the non-dropout consumers off each other's and off the dropout sites' keys when their
 // (seed, t) / (seed, offset) agree -- without them the waypoint draw (b, 0) was the nav draw u0 of sample 2 b.
 //
@@ -209,6 +210,7 @@ __host__ __device__ __forceinline__ uint32_t bb_site_key(uint64_t seed, uint64_t
 }
 // domain separation of the non-dropout consumers, applied on the host side of the launch
 constexpr uint32_t BB_STREAM_NAV = 0x6e617631u, BB_STREAM_WAYPOINT = 0x77617970u, BB_STREAM_GHOST = 0x67687374u;
+constexpr uint32_t BB_STREAM_CE_ACTION = 0x63656163u;      // the CE training rollout's action draw (csrc/ce_train.hip)
 __host__ __device__ __forceinline__ uint32_t bb_stream_key(uint32_t key, uint32_t domain) { return bb_hash32(key ^ domain); }
 // threshold = round(p * 2^16); keep iff the element's 16 random bits >= threshold
 __host__ __device__ __forceinline__ uint32_t bb_drop_threshold(float p) {
