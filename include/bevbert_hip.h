@@ -691,6 +691,35 @@ int bevbert_ce_embeds_bwd(const void* dG, int dtype, int t, int T, int B, int N,
 int bevbert_ce_sample_action(const void* logits, int dtype, int B, int C, const int64_t* teacher, float sample_ratio,
                              uint32_t seed, int t, int64_t* a_t, float* u0, float* u1, hipStream_t stream);
 
+/* ---- Validation metrics (csrc/val_metrics.hip, validate.py; pretrain_src/train_r2r.py:351-510) ------------------------
+ * Accumulated on the device, no atomics: every entry leaves per-row (per-workgroup) records in `scratch` and ONE workgroup
+ * folds them in index order, so two runs give the same bits.  `acc` is three 8-byte words {double sum; int64 a; int64 b}
+ * that the fold ADDS into (zero them per task).  scratch: 8 bytes per row for val_ce_rows / val_bce_keys, 24 KiB for
+ * val_auc; 8-byte aligned; the entries of one accumulator share a stream.
+ *
+ * val_ce_rows: logits (R, C) f32 / bf16 with row stride ld (elements), target (R) i64, valid (R) f32 or NULL.  One pass
+ * per row: running maximum and sum of exponentials in fp32 (-inf entries add nothing), arg-max with the lowest index on a
+ * tie, loss = lse - logit[target].  sum += loss, a += (arg-max == target), b += 1.  A row with valid == 0 adds nothing; a
+ * row with target < 0 (ignore_index; also target >= C) adds no loss and no hit but counts in b -- what
+ * F.cross_entropy(reduction='sum') and len(labels) give.  C <= 1024: one wave per row, else one workgroup per row; 16-byte
+ * loads where a row starts on a 16-byte boundary.  NaN logits are not ranked as torch.argmax ranks them. */
+int bevbert_val_ce_rows(const void* logits, int64_t ld, const int64_t* target, const float* valid, int R, int C, int dtype,
+                        void* acc, void* scratch, hipStream_t stream);
+
+/* val_bce_keys: logits (R, C) f32 / bf16 (row stride ld), labels uint8 rows read through idx (i64, NULL: row r) as in
+ * bce_rows_fwd, valid (R) f32 or NULL.  sum += BCE-with-logits over the valid rows' elements, a += valid rows.  Element
+ * (r, c) leaves keys[cursor + r C + c] = (monotone_u32(logit) << 1) | (label != 0), monotone_u32 = the sign-flip map of the
+ * fp32 bits with -0.0 taken as +0.0 (bf16 is widened exactly); elements of invalid rows leave INT64_MAX.  A position
+ * >= capacity is not written and sets *overflow (i64) to 1.  The caller advances its cursor by R C. */
+int bevbert_val_bce_keys(const void* logits, int64_t ld, const uint8_t* labels, const int64_t* idx, const float* valid, int R,
+                         int C, int dtype, void* acc, void* scratch, int64_t* keys, int64_t cursor, int64_t capacity,
+                         int64_t* overflow, hipStream_t stream);
+
+/* val_auc: keys ascending (n < 2^31), INT64_MAX entries skipped.  out[0] = 2U, out[1] = P, out[2] = N (stored, not
+ * added): U the Mann-Whitney statistic of the positives with ties (equal key >> 1) at their mid-rank, exact in integers;
+ * AUC = out[0] / (2 P N). */
+int bevbert_val_auc(const int64_t* sorted_keys, int64_t n, int64_t* out, void* scratch, hipStream_t stream);
+
 /* ---- CLIP vision transformer (csrc/vit.hip, clip_vit.py): forward-only row kernels ------------------------------------
  * Rows are (rows, H) row-major, H in {256, 512, 768, 1024}; the residual stream z32 is fp32 whatever `dtype` (the
  * compute dtype of the GEMM operands: BB_F32 or BB_BF16). */

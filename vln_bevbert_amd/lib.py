@@ -19,7 +19,7 @@ CSRC = os.path.join(_HERE, "csrc")
 # instructions of the SIMD's other wave while plain ones do (scripts/probes/mfma_valu_overlap.hip,
 # profiles/r05_mfma_valu_overlap_probe.txt).  Measured on that kernel: no difference either way.
 EXTRA_FLAGS = {"attn_fwd4.hip": ["-fno-slp-vectorize"]}
-SOURCES = ["splat.hip", "rowops.hip", "attn_simple.hip", "attn_f32.hip", "attn_mfma.hip", "attn_bwd1.hip", "attn_fwd2.hip", "attn_fwd4.hip", "attn_bwd2.hip", "attn_bwd3.hip", "attn_small.hip", "attn_short.hip", "smallk.hip", "sap_loss.hip", "graph_nav.hip", "nav_expert.hip", "waypoint.hip", "ce_map.hip", "ce_train.hip", "vit.hip", "depth_resnet.hip", "gemm.hip", "capi.hip"]
+SOURCES = ["splat.hip", "rowops.hip", "attn_simple.hip", "attn_f32.hip", "attn_mfma.hip", "attn_bwd1.hip", "attn_fwd2.hip", "attn_fwd4.hip", "attn_bwd2.hip", "attn_bwd3.hip", "attn_small.hip", "attn_short.hip", "smallk.hip", "sap_loss.hip", "graph_nav.hip", "nav_expert.hip", "waypoint.hip", "ce_map.hip", "ce_train.hip", "val_metrics.hip", "vit.hip", "depth_resnet.hip", "gemm.hip", "capi.hip"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "bevbert_hip.h")
 
 F32, BF16, F16 = 0, 1, 2
@@ -157,6 +157,9 @@ _PROTOS = {
     "bevbert_ce_tape_record": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "bevbert_ce_embeds_bwd": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I] + [_P] * 9,
     "bevbert_ce_sample_action": [_P, _I, _I, _I, _P, _F, ctypes.c_uint32, _I, _P, _P, _P, _P],
+    "bevbert_val_ce_rows": [_P, _I64, _P, _P, _I, _I, _I, _P, _P, _P],
+    "bevbert_val_bce_keys": [_P, _I64, _P, _P, _P, _I, _I, _I, _P, _P, _P, _I64, _I64, _P, _P],
+    "bevbert_val_auc": [_P, _I64, _P, _P, _P],
     "bevbert_vit_patchify": [_P, _P, _P, _I, _I, _I, _I, _P, _I, _P],
     "bevbert_vit_embed_prenorm": [_P] * 9 + [_I, _I, _I, _F, _I, _P],
     "bevbert_vit_bias_residual_prenorm": [_P] * 7 + [_I, _I, _I, _F, _I, _I, _P],

@@ -516,6 +516,13 @@ class PretrainTrainer:
         self.optimizer_step()
         return loss
 
+    def validate(self, val_loaders, setname="", **kw):
+        """train_r2r.py:351-369 on the device (validate.py): losses, accuracies and the exact AUC of every task of
+        ``val_loaders`` ({task: iterable of batches}), one read-back per task.  Eager, under no_grad, in eval() mode; the
+        training state (parameters, moments, step counter, captured graphs) is not touched."""
+        from .validate import validate
+        return validate(self.model, val_loaders, setname, **kw)
+
     # ---- captured steps ----------------------------------------------------------------------------------------
     GRAPH_WARMUP = 2
 
