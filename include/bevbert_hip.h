@@ -366,9 +366,11 @@ int bevbert_dropout_add(const void* x, const void* residual, void* y, int64_t n,
  * fw = sigmoid(fuse_raw) (fuse_raw NULL: 0.5); global logits = global_raw * fw with -inf on visited nodes and beyond
  * gmap_lens; local logits = local_raw * (1 - fw) with -inf where nav_masks[b, cand_idxs[b, k]] == 0; fused logits =
  * global + [local | sum of local over vis_c | 0][src]; loss[b] = CE(global) + CE(local) + CE(fused) (labels:
- * global_labels twice, local_labels).  dG (B,G) / dL (B,K) / dF (B): fp32 gradients w.r.t. global_raw / local_raw /
- * fuse_raw for dloss[b] = 1.  bool tensors are bytes.  G <= 64, K <= 62.  bevbert_sap_loss_bwd: d_*_raw = d* * dloss[b]
- * in the heads' dtype (d_fuse_raw may be NULL). */
+ * global_labels twice, local_labels).  A label of -100 is ignored as by F.cross_entropy's ignore_index: global -100
+ * drops the global and the fused term, local -100 the local term; a dropped term adds 0 to loss[b] and nothing to dG /
+ * dL / dF, the other terms are unchanged; other labels outside [0, G) / [0, K) are the caller's error.  dG (B,G) /
+ * dL (B,K) / dF (B): fp32 gradients w.r.t. global_raw / local_raw / fuse_raw for dloss[b] = 1.  bool tensors are
+ * bytes.  G <= 64, K <= 62.  bevbert_sap_loss_bwd: d_*_raw = d* * dloss[b] in the heads' dtype (d_fuse_raw may be NULL). */
 int bevbert_sap_loss_fwd(const void* global_raw, const void* local_raw, const void* fuse_raw, const uint8_t* visited,
                          const int64_t* gmap_lens, const uint8_t* nav_masks, const int64_t* cand_idxs, const int64_t* src,
                          const uint8_t* vis_c, const int64_t* global_labels, const int64_t* local_labels, float* loss,
@@ -378,8 +380,11 @@ int bevbert_sap_loss_bwd(const float* dG, const float* dL, const float* dF, cons
 
 /* F.cross_entropy(logits.float(), target, reduction="none") on wide rows -- the MLM head (pretrain_cmt.py:262-266,
  * rows = masked tokens, C = vocabulary): logits are read in their own dtype (bf16 / fp32, rows x C contiguous, base
- * 16-byte aligned, any C), statistics in fp32; loss[r] and lse[r] out.  bwd: dlogits = (softmax - onehot) * dloss[r]
- * in the logits' dtype (dlogits may alias logits). */
+ * 16-byte aligned, any C), statistics in fp32; loss[r] out, and lse (2 x rows floats) = the row maxima m[r] followed by
+ * log sum_c exp(logits[r, c] - m[r]), kept apart so that the backward's softmax does not inherit the rounding of their
+ * sum at the size of m.  bwd: lse as the forward left it; dlogits = (softmax - onehot) * dloss[r] in the logits' dtype
+ * (dlogits may alias logits).  Targets must lie in [0, C): there is no ignore_index here, static batches pad their rows
+ * with target 0 and weight 0 (static_step.py:174). */
 int bevbert_cross_entropy_fwd(const void* logits, const int64_t* target, float* loss, float* lse, int rows, int C,
                               int dtype, hipStream_t stream);
 int bevbert_cross_entropy_bwd(const void* logits, const int64_t* target, const float* lse, const float* dloss,

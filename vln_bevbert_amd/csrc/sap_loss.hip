@@ -5,6 +5,10 @@
 //   local logits     ll = local_raw * (1 - fw),   -inf where the candidate's BEV cell is not navigable
 //   fused logits     fu = gl + [ll | sum of ll over visited candidates | 0][src]     (vilmodel-side vpid matching: src)
 //   loss             CE(gl, global label) + CE(ll, local label) + CE(fu, global label)
+// A label of -100 is F.cross_entropy's ignore_index (the dataset's "no target", pretrain_src/data/dataset.py:132-156):
+// a global label of -100 drops the global and the fused term, a local label of -100 the local term.  A dropped term
+// adds 0 to the loss and nothing to any gradient; the sample's other terms are unchanged.  Any other label outside
+// [0, G) / [0, K) is the caller's error, as it is in torch.
 // In PyTorch this is ~35 elementwise / reduction launches forward and as many backward, each on a (B, <= 64) tensor.
 // One wave per sample does all of it: lane j owns global-map node j and BEV candidate j.  The kernel also leaves the
 // gradients w.r.t. the three head outputs for a unit upstream gradient; sap_loss_grad scales them by dloss[b].
@@ -23,6 +27,7 @@ __global__ __launch_bounds__(64) void sap_loss_kernel(const T* __restrict__ graw
   const int b = blockIdx.x, lane = threadIdx.x;
   const float fw = fraw ? 1.0f / (1.0f + __expf(-io<T>::ld(fraw + b))) : 0.5f;
   const int gt = (int)glabel[b], lt = (int)llabel[b];
+  const bool g_on = gt != -100, l_on = lt != -100;          // ignore_index: selects below, never a product with 0
   // global branch
   const bool gv = lane < G;
   const float gr = gv ? io<T>::ld(graw + (size_t)b * G + lane) : 0.f;
@@ -44,12 +49,13 @@ __global__ __launch_bounds__(64) void sap_loss_kernel(const T* __restrict__ graw
   const float eg = __expf(gl - mg), el = __expf(ll - ml), ef = __expf(fu - mf);      // exp(-inf - m) = 0
   const float sg = wave_sum(eg), sl = wave_sum(el), sf = wave_sum(ef);
   const float lse_g = mg + __logf(sg), lse_l = ml + __logf(sl), lse_f = mf + __logf(sf);
-  const float gl_t = __shfl(gl, gt, 64), ll_t = __shfl(ll, lt, 64), fu_t = __shfl(fu, gt, 64);
-  if (lane == 0) loss[b] = (lse_g - gl_t) + (lse_l - ll_t) + (lse_f - fu_t);
+  const float gl_t = __shfl(gl, g_on ? gt : 0, 64), ll_t = __shfl(ll, l_on ? lt : 0, 64);
+  const float fu_t = __shfl(fu, g_on ? gt : 0, 64);
+  if (lane == 0) loss[b] = (g_on ? lse_g - gl_t : 0.f) + (l_on ? lse_l - ll_t : 0.f) + (g_on ? lse_f - fu_t : 0.f);
   // gradients for dloss[b] = 1
   const float pg = eg / sg, pl = el / sl, pf = ef / sf;
-  const float dfu = gv ? pf - (lane == gt ? 1.f : 0.f) : 0.f;
-  const float dgl = gv ? (pg - (lane == gt ? 1.f : 0.f)) + dfu : 0.f;
+  const float dfu = gv && g_on ? pf - (lane == gt ? 1.f : 0.f) : 0.f;
+  const float dgl = gv && g_on ? (pg - (lane == gt ? 1.f : 0.f)) + dfu : 0.f;
   float dext = 0.f, dext_bw = 0.f;            // gather's backward: lane k sums the fused gradients routed to candidate k
   for (int j = 0; j < G; ++j) {               // in node order: the summation order is fixed
     const int sj = __shfl(s, j, 64);
@@ -57,7 +63,7 @@ __global__ __launch_bounds__(64) void sap_loss_kernel(const T* __restrict__ graw
     if (sj == lane && lane < K) dext += dj;
     if (sj == K) dext_bw += dj;
   }
-  const float dll = lv ? (pl - (lane == lt ? 1.f : 0.f)) + dext + (vc ? dext_bw : 0.f) : 0.f;
+  const float dll = lv ? (l_on ? pl - (lane == lt ? 1.f : 0.f) : 0.f) + dext + (vc ? dext_bw : 0.f) : 0.f;
   const float dgr = gmasked ? 0.f : dgl * fw;
   const float dlr = lmasked ? 0.f : dll * (1.0f - fw);
   if (gv) dG[(size_t)b * G + lane] = dgr;
@@ -115,7 +121,8 @@ BEVBERT_API int bevbert_sap_loss_bwd(const float* dG, const float* dL, const flo
 // Row-wise cross-entropy on wide rows (the MLM head: rows = masked tokens, C = vocabulary; pretrain_cmt.py:262-266
 // F.cross_entropy(scores, labels, reduction="none") on fp32 copies of the logits).  Reads the head's logits in their
 // own dtype, accumulates in fp32: forward = one pass for the maximum, one for the sum (the row stays in L2), loss and
-// log-sum-exp out; backward writes d logits = (softmax - onehot) * dloss[row] in the logits' dtype.
+// the log-sum-exp out, the latter as its two halves (lse[row] = the row maximum m, lse[rows + row] = log sum exp(x - m));
+// backward writes d logits = (softmax - onehot) * dloss[row] in the logits' dtype.
 // =============================================================================================
 // A row starts at element row * C: the 4-wide loads begin at the first element whose index is a multiple of 4 (the
 // vocabularies of the shipped configurations, 30 522 and 250 002, are not), scalars cover the ragged ends.
@@ -156,9 +163,10 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const T* __restrict__ logit
   if ((tid & 63) == 0) sh[tid >> 6] = s;
   __syncthreads();
   if (tid == 0) {
-    const float l = m + __logf((sh[0] + sh[1]) + (sh[2] + sh[3]));
-    lse[row] = l;
-    loss[row] = l - io<T>::ld(x + target[row]);
+    const float ls = __logf((sh[0] + sh[1]) + (sh[2] + sh[3]));
+    lse[row] = m;                        // the two halves of the log-sum-exp, see ce_bwd_kernel
+    lse[gridDim.x + row] = ls;
+    loss[row] = (m + ls) - io<T>::ld(x + target[row]);
   }
 }
 
@@ -170,21 +178,25 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const T* __restrict__ logit
   const T* x = logits + (size_t)row * C;
   T* d = dlogits + (size_t)row * C;
   const CeSpan sp = ce_span(row, C);
-  const float l = lse[row], g = dloss[row];
+  // softmax = exp((x - m) - log s): x - m is exact near the maximum, where the probabilities are large.  exp(x - lse)
+  // would carry the rounding of lse = m + log s at the size of m -- 1.5e-5 of every probability at |m| = 300.
+  const float m = lse[row], ls = lse[gridDim.x + row], g = dloss[row];
   const int t = (int)target[row];
   for (int v = tid; v < sp.nvec; v += 256) {
     const int c = sp.head + 4 * v;
     const float4 q = ld4<T>(x + c);
-    float4 o = make_float4(__expf(q.x - l) * g, __expf(q.y - l) * g, __expf(q.z - l) * g, __expf(q.w - l) * g);
+    float4 o = make_float4(__expf((q.x - m) - ls) * g, __expf((q.y - m) - ls) * g, __expf((q.z - m) - ls) * g,
+                           __expf((q.w - m) - ls) * g);
     if (t == c) o.x -= g;
     if (t == c + 1) o.y -= g;
     if (t == c + 2) o.z -= g;
     if (t == c + 3) o.w -= g;
     st4<T>(d + c, o);
   }
-  for (int c = tid; c < sp.head; c += 256) io<T>::st(d + c, (__expf(io<T>::ld(x + c) - l) - (c == t ? 1.f : 0.f)) * g);
+  for (int c = tid; c < sp.head; c += 256)
+    io<T>::st(d + c, (__expf((io<T>::ld(x + c) - m) - ls) - (c == t ? 1.f : 0.f)) * g);
   for (int c = sp.tail0 + tid; c < C; c += 256)
-    io<T>::st(d + c, (__expf(io<T>::ld(x + c) - l) - (c == t ? 1.f : 0.f)) * g);
+    io<T>::st(d + c, (__expf((io<T>::ld(x + c) - m) - ls) - (c == t ? 1.f : 0.f)) * g);
 }
 
 BEVBERT_API int bevbert_cross_entropy_fwd(const void* logits, const int64_t* target, float* loss, float* lse, int rows,

@@ -384,7 +384,7 @@ class _CrossEntropy(torch.autograd.Function):
     def forward(ctx, logits, target):
         rows, C = logits.shape
         logits = logits.contiguous()
-        out = torch.empty(2, rows, dtype=torch.float32, device=logits.device)
+        out = torch.empty(3, rows, dtype=torch.float32, device=logits.device)      # loss | row maximum | log sum exp(x - max)
         call("bevbert_cross_entropy_fwd", ptr(logits), ptr(target.contiguous()), ptr(out[0]), ptr(out[1]), rows, C,
              dtype_code(logits), stream())
         ctx.save_for_backward(logits, target, out)
