@@ -127,5 +127,5 @@ def test_sampler_restatement_rule():
 def test_new_entry_points_are_declared_and_typed():
     from vln_bevbert_amd import lib
     names = {"bevbert_ce_tape_record", "bevbert_ce_embeds_bwd", "bevbert_ce_sample_action"}
-    assert names <= set(lib.header_symbols()) and names <= set(lib._PROTOS)
+    assert names <= set(lib.prototypes())
     assert "ce_train.hip" in lib.SOURCES

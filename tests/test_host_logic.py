@@ -20,16 +20,80 @@ def test_library_builds_loads_and_exports_header_symbols():
     lib.build()
     l = lib.load()
     assert l.bevbert_version() >= 100 and l.bevbert_arch() == b"gfx950"
-    syms = lib.header_symbols()
-    assert len(syms) >= 20
-    missing = [s for s in syms if not hasattr(l, s)]
-    assert not missing, missing
-    # every typed prototype exists in the header and vice versa (bar the three untyped getters)
-    assert set(lib._PROTOS) | {"bevbert_last_error", "bevbert_version", "bevbert_arch", "bevbert_hip_error_reset",
-                               "bevbert_colsum_workspace_floats", "bevbert_gemm_plan_count", "bevbert_gemm_rejected_count",
-                               "bevbert_gemm_plan", "bevbert_colsum_partial_rows", "bevbert_gemm_tuning_export",
-                               "bevbert_attn_drop_bits_words", "bevbert_attn_last_path", "bevbert_smallk_workspace_floats",
-                               "bevbert_gemm_tuning_import", "bevbert_attn_plan", "bevbert_attn_bits_ahead"} == set(syms)
+    protos = lib.prototypes()
+    assert len(protos) >= 20
+    # the parser covers exactly the names the header holds: nothing is skipped, nothing invented
+    with open(lib.HEADER) as f:
+        assert set(protos) == set(re.findall(r"\b(bevbert_\w+)\s*\(", f.read()))
+    # every one resolves in the loaded library and carries the derived typing
+    for name, (restype, argtypes) in protos.items():
+        fn = getattr(l, name)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
+
+
+def test_representative_prototypes_are_what_the_header_declares():
+    """One entry per type kind, written out: a parser regression cannot hide behind the parser's own output."""
+    P, S, I, I64, U64, U32, F, D = (ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int64, ctypes.c_uint64,
+                                    ctypes.c_uint32, ctypes.c_float, ctypes.c_double)
+    want = {
+        # uint64_t seed / offset, const int64_t* strides, uint64_t* drop_bits
+        "bevbert_attn_fwd": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, F, I, I, F, U64, U64, P, I, P]),
+        # int and int64_t interleaved
+        "bevbert_gemm": (I, [P, P, P, P, I, I, I, I, I, I64, I64, I64, I, I64, I64, I64, I, I, I, F, P, I64, I, P]),
+        # double by value
+        "bevbert_nav_metrics": (I, [P, I, I, P, P, P, I, P, P, P, I, I, D, P, P, P]),
+        # struct pointer, double, double, uint32_t
+        "bevbert_ce_update": (I, [P, P, P, P, P, P, P, I, P, P, P, I, D, D, U32, P, P]),
+        # char* and an int64_t return
+        "bevbert_gemm_tuning_export": (I64, [S, I64]),
+        # const char* return, one float among ints
+        "bevbert_attn_plan": (S, [I, I, I, I, I, I, I, I, F, I, I, I, I, I]),
+        "bevbert_attn_drop_bits_words": (I64, [I, I, I, I]),
+        # struct pointer first
+        "bevbert_gm_update": (I, [P, P, P, P, P, P, P, P, P, P, I, I, P, P, P]),
+        # (void)
+        "bevbert_last_error": (S, []),
+    }
+    protos = lib.prototypes()
+    for name, (restype, argtypes) in want.items():
+        assert protos[name][0] is restype and protos[name][1] == argtypes, (name, protos[name])
+
+
+def test_header_parser_is_strict():
+    I, P = ctypes.c_int, ctypes.c_void_p
+    good = ("typedef struct st { double* a; /* (B) */ int B, N; } st;\n"
+            "int bevbert_a(const st* s, const float* x, int64_t n, hipStream_t stream);\n"
+            "const char* bevbert_b(void);\n")
+    protos, structs = lib.parse_header(good)
+    assert protos == {"bevbert_a": (I, [P, P, ctypes.c_int64, P]), "bevbert_b": (ctypes.c_char_p, [])}
+    assert structs == {"st": [("a", P), ("B", I), ("N", I)]}
+    for bad in ("int bevbert_a(const float* x, size_t n);\n",                      # a type outside the map
+                "int bevbert_a(const size_t* x, int n);\n",                        # ... also behind a pointer
+                "int bevbert_a(const float* x, int n)\nint bevbert_b(void);\n",    # no terminating ;
+                "int bevbert_a(int n)\n",
+                "typedef struct st { double* a; float scale; int B; } st;\n",      # a field that is neither pointer nor int
+                "int bevbert_a(int n);\nstatic\nint bevbert_b(void);\n",           # stray text between declarations
+                "int bevbert_a(int n);\n}\n",
+                "int bevbert_a(int);\n",                                           # unnamed parameter
+                "int bevbert_a();\n"):                                             # no prototype
+        with pytest.raises(lib.BevBertHipError):
+            lib.parse_header(bad)
+            pytest.fail(f"parsed: {bad!r}")
+
+
+def test_state_structs_are_the_headers():
+    from vln_bevbert_amd import ce_map, graph_map_dev
+    gm, ce = lib.struct("bevbert_gm_state"), lib.struct("bevbert_ce_state")
+    assert graph_map_dev._GmState is gm and ce_map._CeState is ce
+    assert ctypes.sizeof(gm) == 96 and ctypes.sizeof(ce) == 192        # 10 pointers + 4 ints; 21 pointers + 6 ints
+    assert [n for n, _ in gm._fields_] == ["pos", "dis", "point", "hops", "visited", "step_ids", "pc_list", "npc", "node_row",
+                                           "node_T", "B", "N", "V", "pad"]
+    assert [t for _, t in gm._fields_] == [ctypes.c_void_p] * 10 + [ctypes.c_int] * 4
+    assert len(ce_map._PTRS) == 21 and ce_map._PTRS[0] == "node_pos" and ce_map._PTRS[-1] == "overflow"
+    assert [n for n, _ in ce._fields_] == list(ce_map._PTRS) + ["B", "N", "Gh", "P", "H", "dtype"]
+    assert [t for _, t in ce._fields_] == [ctypes.c_void_p] * 21 + [ctypes.c_int] * 6
+    with pytest.raises(lib.BevBertHipError):
+        lib.struct("bevbert_no_such_state")
 
 
 # The attention dispatch as a table: (B, Lq, Lk, dtype, impl, graph bias, dropout p, keep-bit workspace, knobs) ->

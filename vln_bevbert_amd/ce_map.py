@@ -34,13 +34,8 @@ from . import ops
 from .pretrain_cmt import bevpos_polar
 from .synthetic import pose_matrix
 
-_PTRS = ("node_pos", "edge_w", "dist", "hops", "pred", "n_nodes", "node_step", "stop_score", "node_embeds", "g_cnt",
-         "g_alive", "g_npos", "g_pos", "g_mean", "g_aug", "g_sum", "g_fronts", "prev_vp", "cur_vp", "merge", "overflow")
-
-
-class _CeState(ctypes.Structure):
-    """bevbert_ce_state (include/bevbert_hip.h)."""
-    _fields_ = [(n, ctypes.c_void_p) for n in _PTRS] + [(n, ctypes.c_int) for n in ("B", "N", "Gh", "P", "H", "dtype")]
+_CeState = lib.struct("bevbert_ce_state")
+_PTRS = tuple(n for n, ct in _CeState._fields_ if ct is ctypes.c_void_p)      # the device arrays, in the struct's order
 
 
 class CEGraphMap:

@@ -10,32 +10,7 @@
 //   (d) bevbert_ce_stop_scores / bevbert_ce_teacher / bevbert_ce_act
 //   (e) bevbert_ce_remember / bevbert_ce_bev_select   update_node_pc's store, gather_node_pc's node choice
 // Ids in outputs: -1 = [stop] / none, k < N = node k, N + g = ghost g.
-#include "common.h"
-
-struct bevbert_ce_state {     // mirrors bevbert_ce_state (include/bevbert_hip.h)
-  double* node_pos;           // (B,N,3)
-  double* edge_w;             // (B,N,N), < 0 = no edge
-  double* dist;               // (B,N,N) shortest_dist, +inf = unreachable / padding
-  int* hops;                  // (B,N,N) len(shortest_path[x][y]), 0 = none
-  int* pred;                  // (B,N,N) predecessor of y on the path from x, -1 = none
-  int* n_nodes;               // (B)
-  int* node_step;             // (B,N)
-  float* stop_score;          // (B,N)
-  void* node_embeds;          // (B,N,H) dtype
-  int* g_cnt;                 // (B) ghosts ever created
-  uint8_t* g_alive;           // (B,Gh)
-  int* g_npos;                // (B,Gh) observed positions = fronts = embedding count
-  double* g_pos;              // (B,Gh,P,3)
-  double* g_mean;             // (B,Gh,3)
-  double* g_aug;              // (B,Gh,3)
-  float* g_sum;               // (B,Gh,H)
-  int* g_fronts;              // (B,Gh,P)
-  int* prev_vp;               // (B), -1 = none
-  int* cur_vp;                // (B)
-  uint8_t* merge;             // (B) merge_ghost
-  int* overflow;              // (1)
-  int B, N, Gh, P, H, dtype;
-};
+#include "common.h"      // bevbert_ce_state: include/bevbert_hip.h
 
 #define CE_MAX_N 64                 // one lane per Dijkstra source, the settled set is a 64-bit mask
 #define CE_MAX_G 512                // 1 + N + Gh rows of the padded global map held in LDS

@@ -7,10 +7,13 @@
 #include <string.h>
 #include <type_traits>
 
+// The C ABI: every BEVBERT_API definition below is checked against its declaration there, and the state structs and dtype
+// codes are the header's own.
+#include "../../include/bevbert_hip.h"
+
 #define BEVBERT_API extern "C" __attribute__((visibility("default")))
 
-// dtype enum of the C ABI (include/bevbert_hip.h)
-enum { BB_F32 = 0, BB_BF16 = 1, BB_F16 = 2 };
+enum { BB_F32 = BEVBERT_F32, BB_BF16 = BEVBERT_BF16, BB_F16 = BEVBERT_F16 };
 
 // error codes
 enum { BB_OK = 0, BB_EINVAL = -1, BB_ELAUNCH = -2, BB_EUNSUPPORTED = -3 };

@@ -20,19 +20,7 @@
 
 #define GM_INF 95959595.0      // graph_utils.py:46
 
-struct GmState {               // mirrors bevbert_gm_state (include/bevbert_hip.h)
-  double* pos;
-  double* dis;
-  int* point;
-  int* hops;
-  uint8_t* visited;
-  int* step_ids;
-  int* pc_list;
-  int* npc;
-  int* node_row;
-  float* node_T;
-  int B, N, V, pad;
-};
+using GmState = bevbert_gm_state;      // include/bevbert_hip.h
 
 // GraphMap.update_graph (graph_utils.py:109-115) + FloydGraph.add_edge / update (:55-72) for every live episode,
 // agent.py:471-474 (step ids), GraphMap.update_node_pc's bookkeeping (which store row / poses a visited node has), and the

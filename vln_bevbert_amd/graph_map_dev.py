@@ -27,10 +27,7 @@ from . import lib
 from .graph_map import _INF, GraphMapBatch, HostFeed, pose_matrix
 
 
-class _GmState(ctypes.Structure):
-    """bevbert_gm_state (include/bevbert_hip.h)."""
-    _fields_ = [(n, ctypes.c_void_p) for n in ("pos", "dis", "point", "hops", "visited", "step_ids", "pc_list", "npc",
-                                                "node_row", "node_T")] + [(n, ctypes.c_int) for n in ("B", "N", "V", "pad")]
+_GmState = lib.struct("bevbert_gm_state")
 
 
 class _Digest:
@@ -92,8 +89,9 @@ class DeviceGraphMap:
             adj_host[:, :old, :old] = self.adj_host
         self.t, self.N, self.visited_host, self.adj_host = new, N, vis_host, adj_host
         st = _GmState()
-        for k in ("pos", "dis", "point", "hops", "visited", "step_ids", "pc_list", "npc", "node_row", "node_T"):
-            setattr(st, k, new[k].data_ptr())
+        for k, ct in _GmState._fields_:
+            if ct is ctypes.c_void_p:
+                setattr(st, k, new[k].data_ptr())
         st.B, st.N, st.V, st.pad = B, N, self.V, 0
         self.state = st
         self._st_ptr = ctypes.addressof(st)

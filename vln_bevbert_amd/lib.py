@@ -1,10 +1,12 @@
-"""ctypes binding of libbevbert_hip.so (C ABI: include/bevbert_hip.h).
+"""ctypes binding of libbevbert_hip.so, derived from its C ABI: include/bevbert_hip.h is parsed once per process and
+gives every entry point its restype / argtypes and both state structs their fields -- nothing of the ABI is typed here.
 
 The shared library is built in-tree by ``__graft_entry__.build()`` (hipcc --offload-arch=gfx950).
 There is deliberately NO fallback: if the library is missing or a call fails, an exception is raised --
 this package never routes work to PyTorch eager kernels or to the CPU oracle.
 """
 import ctypes
+import functools
 import os
 import re
 import subprocess
@@ -41,7 +43,7 @@ def build(force=False, verbose=False):
     """Compile csrc/*.hip into libbevbert_hip.so for gfx950 (cross-compiles without a GPU): one object per source
     (only the stale ones, in parallel), then one link."""
     from concurrent.futures import ThreadPoolExecutor
-    headers = [os.path.join(CSRC, h) for h in ("common.h", "attn_common.h", "attn_mfma_common.h", "attn_bwd7p1.h")]
+    headers = [os.path.join(CSRC, h) for h in ("common.h", "attn_common.h", "attn_mfma_common.h", "attn_bwd7p1.h")] + [HEADER]
     hdr_time = max(os.path.getmtime(h) for h in headers)
     objdir = os.path.join(_HERE, "_obj")
     os.makedirs(objdir, exist_ok=True)
@@ -67,114 +69,83 @@ def build(force=False, verbose=False):
     return LIB_PATH
 
 
-def header_symbols():
+# ---- the C ABI, read from include/bevbert_hip.h ----------------------------------------------------------------------
+# The header is the only place where a prototype or a state struct is written down.  The map below is closed: a
+# declaration using anything else is an error, never a guess.  Pointers (struct pointers and [] parameters included) are
+# c_void_p, so callers may pass data_ptr() ints, ctypes.addressof results, byref objects and ctypes arrays alike.
+_SCALARS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "uint32_t": ctypes.c_uint32,
+            "float": ctypes.c_float, "double": ctypes.c_double, "hipStream_t": ctypes.c_void_p}
+_POINTEES = {"void", "char", "uint8_t", "int16_t", *_SCALARS}       # and the header's own structs
+_DECL = re.compile(r"""\s*(?: typedef\s+struct\s+\w+\s*\*\s*hipStream_t\s*;                               # the opaque handle
+    | typedef\s+struct\s+\w*\s*\{(?P<body>(?:[^{};]+;)+)\s*\}\s*(?P<struct>\w+)\s*;                       # a state struct
+    | (?P<ret>[\w\s*]+?)\b(?P<fn>\w+)\s*\((?P<params>[^(){};]*)\)\s*; )""", re.X)                        # an entry point
+_VAR = re.compile(r"(?P<type>[\w\s*]+?)\b(?P<names>\w+(?:\s*,\s*\w+)*)\s*(?P<array>\[\d*\])?")
+
+
+def _fail(what):
+    raise BevBertHipError(f"bevbert_hip.h: {what}")
+
+
+def _ctype(decl, structs):
+    base = decl.replace("*", " ").replace("const ", " ").split()
+    if len(base) == 1 and "*" not in decl and base[0] in _SCALARS:
+        return _SCALARS[base[0]]
+    if len(base) == 1 and "*" in decl and (base[0] in _POINTEES or base[0] in structs):
+        return ctypes.c_char_p if base == ["char"] and decl.count("*") == 1 else ctypes.c_void_p
+    _fail(f"unknown type {decl.strip()!r}")
+
+
+def parse_header(text):
+    """(prototypes, structs) of a C header written like include/bevbert_hip.h: {name: (restype, [argtypes])} for every
+    ``ret name(params);`` and {name: [(field, ctype)]} for every ``typedef struct { ... } name;``.  Strict: anything else
+    that is not a comment, a preprocessor line, the extern "C" braces or hipStream_t's typedef raises."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*|^[ \t]*#[^\n]*", " ", text, flags=re.S | re.M)
+    m = re.fullmatch(r'\s*extern\s+"C"\s*\{(.*)\}\s*', text, re.S)
+    text = (m[1] if m else text).rstrip()
+    protos, structs, pos = {}, {}, 0
+    while pos < len(text):
+        m = _DECL.match(text, pos) or _fail(f"cannot parse {' '.join(text[pos:pos + 80].split())!r}")
+        pos = m.end()
+        if m["struct"]:
+            fields = structs[m["struct"]] = []
+            for f in m["body"].split(";")[:-1]:
+                v = _VAR.fullmatch(f.strip())
+                ct = _ctype(v["type"], structs) if v and not v["array"] else None
+                if not (ct is ctypes.c_int or ct is ctypes.c_void_p and "," not in v["names"]):
+                    _fail(f"{m['struct']}: field {f.strip()!r} is neither a pointer nor int")
+                fields += [(n, ct) for n in v["names"].replace(",", " ").split()]
+        elif m["fn"]:
+            params = [] if m["params"].strip() == "void" else m["params"].split(",")
+            params = [_VAR.fullmatch(p.strip()) or _fail(f"{m['fn']}: cannot parse parameter {p.strip()!r}") for p in params]
+            protos[m["fn"]] = (_ctype(m["ret"], structs), [_ctype(v["type"] + "*" * bool(v["array"]), structs) for v in params])
+    return protos, structs
+
+
+@functools.lru_cache(None)
+def _parsed():
     with open(HEADER) as f:
-        return sorted(set(re.findall(r"\b(bevbert_\w+)\s*\(", f.read())))
+        return parse_header(f.read())
+
+
+def prototypes():
+    """{name: (restype, argtypes)} of every entry point include/bevbert_hip.h declares (parsed once per process)."""
+    return _parsed()[0]
+
+
+@functools.lru_cache(None)
+def struct(name):
+    """The ctypes.Structure of a state struct of the header (bevbert_gm_state, bevbert_ce_state): its fields in
+    declaration order, pointers as c_void_p."""
+    fields = _parsed()[1].get(name) or _fail(f"no struct {name}")
+    return type(name, (ctypes.Structure,), {"_fields_": fields})
 
 
 _lib = None
-_P, _I, _I64, _U64, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float
-
-_PROTOS = {
-    "bevbert_bev_lift_bin": [_P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _F, _F, _P, _P, _P, _P],
-    "bevbert_bev_bin_points": [_P, _P, _I, _I, _I, _F, _F, _P, _P, _P, _P],
-    "bevbert_bev_splat_mean": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _I, _P],
-    "bevbert_attn_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _I, _F, _U64, _U64, _P, _I, _P],
-    "bevbert_attn_drop_bits": [_P, _I, _I, _I, _I, _F, _U64, _U64, _P],
-    "bevbert_attn_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _I, _F,
-                         _U64, _U64, _P, _P],
-    "bevbert_bias_dropout_residual_layernorm_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _I, _F, _U64,
-                                                    _U64, _P],
-    "bevbert_layernorm_post_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _I, _P],
-    "bevbert_layernorm_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _U64, _U64, _I, _P],
-    "bevbert_layernorm_res32_fwd": [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _F, _U64, _U64, _P],
-    "bevbert_layernorm_res32_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _U64, _U64, _I, _I, _P],
-    "bevbert_colsum_any": [_P, _P, _I, _I, _I, _I, _P],
-    "bevbert_sem_select": [_P, _P, _I, _I, _I, _P, _P, _P, _P],
-    "bevbert_bce_rows_fwd": [_P, _P, _P, _P, _I, _I, _I, _P],
-    "bevbert_bce_rows_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
-    "bevbert_weighted_mean_fwd": [_P, _P, _P, _F, _I, _P, _P],
-    "bevbert_weighted_mean_bwd": [_P, _P, _P, _F, _I, _P, _P],
-    "bevbert_layernorm_bwd_add": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _U64, _U64, _I, _P],
-    "bevbert_embed_sum_layernorm_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _F, _U64, _U64, _P],
-    "bevbert_embedding_grad": [_P, _P, _P, _I, _I, _I, _I, _P],
-    "bevbert_rows_gather": [_P, _P, _P, _I, _I, _I, _P],
-    "bevbert_graph_bias_fwd": [_P, _P, _P, _P, _I64, _P],
-    "bevbert_graph_bias_bwd": [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P],
-    "bevbert_smallk_linear_layernorm_fwd": [_P] * 11 + [_I, _I, _I, _F, _I, _P],
-    "bevbert_smallk_linear_layernorm_bwd": [_P] * 12 + [_I, _I, _I, _I, _P],
-    "bevbert_rows_scatter": [_P, _P, _P, _I, _I, _I, _I, _P],
-    "bevbert_embedding_grad_sliced": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "bevbert_bias_gelu_fwd": [_P, _P, _P, _I, _I, _I, _P],
-    "bevbert_bias_gelu_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "bevbert_bias_relu_fwd": [_P, _P, _P, _I, _I, _I, _P],
-    "bevbert_bias_relu_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "bevbert_colsum": [_P, _P, _P, _I, _I, _I, _I, _P],
-    "bevbert_segment_wsum": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
-    "bevbert_grad_norm_clip": [_P, _I64, _F, _F, _P, _P, _P],
-    "bevbert_adamw_step": [_P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _F, _F, _F, _F, _F, _P],
-    "bevbert_set_step_salt": [_P],
-    "bevbert_colsum_partials": [_P, _P, _I, _I, _I, _P],
-    "bevbert_multi_finalize": [_P, _I, _P],
-    "bevbert_multi_accum": [_P, _I, _P],
-    "bevbert_cast_f32": [_P, _P, _I64, _I, _P],
-    "bevbert_zero": [_P, _I64, _P],
-    "bevbert_accum_partials": [_P, _P, _I, _I64, _I, _P],
-    "bevbert_dropout_keep_mask": [_P, _I64, _F, _U64, _U64, _P],
-    "bevbert_gemm": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I64, _I64, _I64, _I, _I64, _I64, _I64, _I, _I, _I, _F, _P,
-                     _I64, _I, _P],
-    "bevbert_colsum_finalize": [_P, _I, _I, _I, _P, _P, _P, _I, _P],
-    "bevbert_dropout_add": [_P, _P, _P, _I64, _I, _I, _F, _U64, _U64, _P],
-    "bevbert_gm_update": [_P] * 10 + [_I, _I, _P, _P, _P],
-    "bevbert_gm_nav_vars": [_P] * 7 + [_I, _I, _I] + [_P] * 7,
-    "bevbert_gm_bev_select": [_P, _P, _I, _I, _P, _P, _P, _P, _P],
-    "bevbert_gm_gather_views": [_P, _P, _P, _P, _I, _I64, _P],
-    "bevbert_gm_embed_update": [_P] * 9 + [_I, _I, _I, _I, _P],
-    "bevbert_gm_node_embeds": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P],
-    "bevbert_sap_loss_fwd": [_P] * 15 + [_I, _I, _I, _I, _I, _P],
-    "bevbert_sap_loss_bwd": [_P] * 7 + [_I, _I, _I, _I, _P],
-    "bevbert_cross_entropy_fwd": [_P, _P, _P, _P, _I, _I, _I, _P],
-    "bevbert_cross_entropy_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
-    "bevbert_gemm_run": [_I, _P, _P, _P, _P, _P, _I64, _P],
-    "bevbert_gemm_run_add": [_I, _P, _P, _P, _P, _P, _P, _I64, _P],
-    "bevbert_nav_expert": [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P],
-    "bevbert_nav_action": [_P, _I, _I, _I, _I, _I, _I] + [_P] * 10 + [_I, _F, ctypes.c_uint32] + [_P] * 7,
-    "bevbert_nav_ce_fwd": [_P, _P, _P, _I, _I, _I, _I, _P],
-    "bevbert_nav_ce_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "bevbert_nav_traj_append": [_P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P],
-    "bevbert_nav_metrics": [_P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _I, ctypes.c_double, _P, _P, _P],
-    "bevbert_wp_ring_attn": [_P, _P, _I, _I, _F, _I, _P],
-    "bevbert_wp_candidates": [_P, _I, _I, ctypes.c_uint32, _I] + [_P] * 11,
-    "bevbert_wp_pano_inputs": [_P, _P, _I, _I] + [_P] * 12,
-    "bevbert_ce_update": [_P] * 7 + [_I, _P, _P, _P, _I, ctypes.c_double, ctypes.c_double, ctypes.c_uint32, _P, _P],
-    "bevbert_ce_nav_vars": [_P] * 12,
-    "bevbert_ce_bev_cands": [_P, _P, _P, _I, ctypes.c_double, _I] + [_P] * 8,
-    "bevbert_ce_stop_scores": [_P, _P, _P, _I, _P],
-    "bevbert_ce_teacher": [_P] * 6,
-    "bevbert_ce_act": [_P, _P, _P, _P, _I, _I, _P, _P],
-    "bevbert_ce_remember": [_P, _P, _P, _P, _I64, _P],
-    "bevbert_ce_bev_select": [_P, _P, _I, _I, _P, _P, _P],
-    "bevbert_ce_tape_record": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
-    "bevbert_ce_embeds_bwd": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I] + [_P] * 9,
-    "bevbert_ce_sample_action": [_P, _I, _I, _I, _P, _F, ctypes.c_uint32, _I, _P, _P, _P, _P],
-    "bevbert_val_ce_rows": [_P, _I64, _P, _P, _I, _I, _I, _P, _P, _P],
-    "bevbert_val_bce_keys": [_P, _I64, _P, _P, _P, _I, _I, _I, _P, _P, _P, _I64, _I64, _P, _P],
-    "bevbert_val_auc": [_P, _I64, _P, _P, _P],
-    "bevbert_vit_patchify": [_P, _P, _P, _I, _I, _I, _I, _P, _I, _P],
-    "bevbert_vit_embed_prenorm": [_P] * 9 + [_I, _I, _I, _F, _I, _P],
-    "bevbert_vit_bias_residual_prenorm": [_P] * 7 + [_I, _I, _I, _F, _I, _I, _P],
-    "bevbert_vit_bias_quickgelu": [_P, _P, _P, _I, _I, _I, _P],
-    "bevbert_depth_grid_pool": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "bevbert_dr_stem": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "bevbert_dr_gn_stats": [_P, _P, _I64, _P, _P, _I, _I, _I, _I, _F, _I, _P],
-    "bevbert_dr_gn_apply": [_P] * 11 + [_I, _I, _I, _I, _I, _I, _P],
-    "bevbert_dr_gn_relu_maxpool": [_P] * 6 + [_I, _I, _I, _I, _I, _I, _P],
-    "bevbert_dr_gather_rows": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-}
 
 
 def load():
-    """dlopen the library and type every entry point. Raises if it has not been built."""
+    """dlopen the library and type every entry point as the header declares it. Raises if it has not been built, or if
+    it does not export a declared symbol."""
     global _lib
     if _lib is not None:
         return _lib
@@ -183,36 +154,12 @@ def load():
             f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
             "(there is no PyTorch/CPU fallback for the hot path)")
     lib = ctypes.CDLL(LIB_PATH)
-    lib.bevbert_last_error.restype = ctypes.c_char_p
-    lib.bevbert_arch.restype = ctypes.c_char_p
-    lib.bevbert_version.restype = _I
-    lib.bevbert_attn_last_path.restype = ctypes.c_char_p
-    lib.bevbert_attn_last_path.argtypes = [_I]
-    lib.bevbert_attn_plan.restype = ctypes.c_char_p
-    lib.bevbert_attn_plan.argtypes = [_I] * 8 + [_F] + [_I] * 5
-    lib.bevbert_attn_bits_ahead.restype = _I
-    lib.bevbert_attn_bits_ahead.argtypes = [_I, _I, _I]
-    lib.bevbert_hip_error_reset.restype = _I
-    lib.bevbert_colsum_workspace_floats.restype = _I64
-    lib.bevbert_colsum_workspace_floats.argtypes = [_I]
-    lib.bevbert_gemm_plan_count.restype = _I
-    lib.bevbert_gemm_rejected_count.restype = _I
-    lib.bevbert_gemm_tuning_export.restype = _I64
-    lib.bevbert_gemm_tuning_export.argtypes = [ctypes.c_char_p, _I64]
-    lib.bevbert_gemm_tuning_import.restype = _I
-    lib.bevbert_gemm_tuning_import.argtypes = [ctypes.c_char_p]
-    lib.bevbert_attn_drop_bits_words.restype = _I64
-    lib.bevbert_attn_drop_bits_words.argtypes = [_I, _I, _I, _I]
-    lib.bevbert_smallk_workspace_floats.restype = _I64
-    lib.bevbert_smallk_workspace_floats.argtypes = [_I, _I, _I]
-    lib.bevbert_colsum_partial_rows.restype = _I
-    lib.bevbert_colsum_partial_rows.argtypes = [_I]
-    lib.bevbert_gemm_plan.restype = _I
-    lib.bevbert_gemm_plan.argtypes = [_I, _I, _I, _I, _I, _I64, _I64, _I64, _I, _I64, _I64, _I64, _I, _I, _I, _I, _I64, _I]
-    for name, args in _PROTOS.items():
-        fn = getattr(lib, name)
-        fn.argtypes = args
-        fn.restype = _I
+    for name, (restype, argtypes) in prototypes().items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            raise BevBertHipError(f"{LIB_PATH} does not export {name}, which bevbert_hip.h declares") from None
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 
