@@ -8,8 +8,8 @@
  *   - every pointer is a DEVICE pointer unless marked "host"; the caller owns all memory, nothing is allocated,
  *     retained or freed here.  Process-wide state, all of it: (1) bevbert_gemm's mutex-guarded plan cache (library
  *     handle + per-shape descriptors), (2) the step-salt POINTER registered by bevbert_set_step_salt (one per process:
- *     two training loops in one process share the salt word -- their masks still differ through their seeds), (3) the
- *     environment switches read by capi.hip (A/B knobs).  Entries may be called concurrently from several threads on
+ *     two training loops in one process share the salt word -- their masks still differ through their seeds) and the slot array
+ *     registered by bevbert_set_fold_norm_slots, (3) the environment switches read by capi.hip (A/B knobs).  Entries may be called concurrently from several threads on
  *     different streams; bevbert_set_step_salt must not race with launches;
  *   - `stream` is a hipStream_t (PyTorch-ROCm: torch.cuda.current_stream().cuda_stream); launches are asynchronous;
  *   - return value 0 = ok, <0 = error (-1 invalid argument, -2 launch failure, -3 unsupported); the message is
@@ -180,8 +180,22 @@ int bevbert_colsum_partials(const void* dy, float* partials, int rows, int C, in
 int bevbert_multi_finalize(const void* tasks, int ntasks, hipStream_t stream);
 /* Batched bevbert_accum_partials: `tasks` = device array of 40-byte records
  * {u64 partials, u64 sink, u64 n4_total, u32 off4, u32 n4, i32 S, i32 dtype}: for the n4 float4 groups starting at
- * off4, sink[i] += sum_{s < S} partials[s * n4_total + off4 + i] (sink already points at the range's first element). */
+ * off4, sink[i] += sum_{s < S} partials[s * n4_total + off4 + i] (sink already points at the range's first element).
+ * The dtype field carries two task flags above the dtype code (bits 0-7); records with them clear behave as above.
+ *   bit 8  STORE: the caller guarantees that the sink range is zero (the gradient arena's fill, nothing added since): the
+ *          sum starts from 0.f -- ((0 + p0) + p1) + ..., bit for bit what accumulating into zeros gives -- and the sink
+ *          is not read.
+ *   bit 9  NORM:  the sum of squares of the values the task stores goes to slots[dtype >> 12] of the array registered
+ *          with bevbert_set_fold_norm_slots (one writer per slot, fixed order, no atomics); ignored when no array is
+ *          registered or the slot lies beyond its capacity. */
 int bevbert_multi_accum(const void* tasks, int ntasks, hipStream_t stream);
+/* The fused gradient norm.  bevbert_set_fold_norm_slots registers (NULL / 0: clears) a device array of `capacity`
+ * floats, process-wide like the step salt; the pointer is read at launch time and passed to the kernels as an argument,
+ * so a captured launch keeps the array it was captured with.  bevbert_sumsq_tasks fills the slots of what no NORM fold
+ * covers: `tasks` = device array of 16-byte records {u64 ptr, u32 n4, u32 slot}, slots[slot] = sum of squares of the
+ * n4 <= 4096 float4 groups at ptr, one workgroup per record. */
+int bevbert_set_fold_norm_slots(float* slots, int capacity);
+int bevbert_sumsq_tasks(const void* tasks, int ntasks, hipStream_t stream);
 
 /* K5  BertEmbeddings.forward (vilmodel.py:62-77): y = LayerNorm(word[ids] + pos[row % L] + type_row) (+dropout). */
 int bevbert_embed_sum_layernorm_fwd(const int64_t* ids, const void* word, const void* pos, const void* type_row,
@@ -300,6 +314,10 @@ int bevbert_segment_wsum(const void* src, const int* rowptr, const int* idx, con
  *   in a hipGraph follows the schedule (optim/sched.py:24-30) without being re-captured. */
 int bevbert_grad_norm_clip(const float* grads, int64_t n, float pre_scale, float max_norm, float* partials,
                            float* scalars, hipStream_t stream);
+/* bevbert_grad_norm_clip's second half alone, over `n` sums of squares that NORM folds and bevbert_sumsq_tasks left in
+ * `slots`: fp64 sum in a fixed order, the same scalars[0..1]. */
+int bevbert_clip_from_slots(const float* slots, int n, float pre_scale, float max_norm, float* scalars,
+                            hipStream_t stream);
 int bevbert_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, void* params_bf16,
                        const uint8_t* chunk_flags, int* chunk_steps, int64_t n, const float* grad_scale_dev,
                        const float* lr_dev, float lr, float beta1, float beta2, float eps, float weight_decay,

@@ -151,7 +151,57 @@ def extra():
     print(json.dumps({"kernel": "ln_bwd_add", "rows": rows, "us": round(t, 2), "bytes": rows * H * 2 * 4, "mark": _mark_idx[0], "GBps": round(rows * H * 8 / t / 1e3, 1)}), flush=True)
 
 
+def fold_real(variants=(("fold", 0),)):
+    """bevbert_multi_accum, isolated, over the task table of one real MLM and one real SAP step (batch 64, full model,
+    store mode as the trainer arms it), and bevbert_sumsq_tasks over that step's complement; three repeats each.
+    ``variants``: (label, bits OR-ed into the dtype word of every bf16 record) -- a kernel experiment is timed in the same
+    process, alternating with the table as built."""
+    import numpy as np
+    from vln_bevbert_amd import synthetic
+    from vln_bevbert_amd.config import BevBertConfig
+    from vln_bevbert_amd.pretrain_cmt import GlocalTextPathCMTPreTraining
+    from vln_bevbert_amd.train import PretrainTrainer
+    cfg = BevBertConfig()
+    torch.manual_seed(0)
+    model = GlocalTextPathCMTPreTraining(cfg)
+    model.tie_weights()
+    arena = model.finalize("cuda", torch.bfloat16, torch.float32)
+    model.train()
+    model.set_dropout(0.1)
+    trainer = PretrainTrainer(model, arena)
+    Q = ops.ReduceQueue
+    for task in ("mlm", "sap"):
+        batch = synthetic.batch_to(synthetic.make_batch(cfg, task, 64, seed=2000, txt_len=80, sems_as="ids"), "cuda")
+        for _ in range(2):                # the second step's scratch addresses are the settled ones
+            Q._accum_tables.clear()
+            trainer.step(task, batch)
+            torch.cuda.synchronize()
+        (entry,) = Q._accum_tables.values()
+        (table, cnt), = entry["tables"]
+        nb = Q.table_bytes[table.data_ptr()]
+        tables = []
+        for label, bits in variants:
+            host = table.cpu().numpy().view(Q._adtype).copy()
+            host["dtype"] |= np.where((host["dtype"] & 0xff) == BF16, bits, 0).astype(np.int32)
+            tables.append((label, torch.from_numpy(host.view(np.uint8)).cuda()))
+        Q.register_slots("cuda")
+        for rep in range(3):
+            for label, tab in tables:
+                t = timeit(lambda: call("bevbert_multi_accum", tab.data_ptr(), cnt, stream()))
+                print(json.dumps({"kernel": f"multi_accum[{label}]", "task": task, "rep": rep, "rows": cnt, "us": round(t, 2), "bytes": nb,
+                                  "GBps": round(nb / t / 1e3, 1)}), flush=True)
+        if entry["nslots"]:
+            comp, ntasks, cb = arena._fold_complement(entry)
+            for rep in range(3):
+                t = timeit(lambda: call("bevbert_sumsq_tasks", comp.data_ptr(), ntasks, stream()))
+                print(json.dumps({"kernel": "sumsq_tasks", "task": task, "rep": rep, "rows": ntasks, "us": round(t, 2), "bytes": cb,
+                                  "GBps": round(cb / t / 1e3, 1)}), flush=True)
+
+
 if __name__ == "__main__":
+    if os.environ.get("ROWOPS_FOLD_REAL", "0") == "1":        # only the fold at a real step's task tables
+        fold_real()
+        sys.exit(0)
     main()
     if os.environ.get("ROWOPS_EXTRA", "1") == "1":
         extra()

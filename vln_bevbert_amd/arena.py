@@ -36,6 +36,8 @@ def _round_up(n, m):
 
 
 class ParamArena:
+    _serial = 0          # arenas made so far in this process (fold_key)
+
     def __init__(self, module, device, compute_dtype=torch.float32, groups=()):
         """groups: iterable of lists of parameter names to lay out contiguously (same decay class)."""
         self.device = torch.device(device)
@@ -112,6 +114,23 @@ class ParamArena:
             p.arena = self
             p.arena_name = n
         self._index = {n: i for i, (n, _) in enumerate(named)}
+        # Fused fold (ops.ReduceQueue.store_ok): element ranges whose gradient only split-K folds write -- parameters with
+        # >= 2 dimensions that are not the weight of an nn.Embedding (embedding_grad_kernel read-modify-writes those rows;
+        # a decoder tied to the word embeddings IS that parameter).  Neighbours in a packed group merge into one range.
+        # ``fold_store`` is the owner's switch: a trainer that zeroes the arena before every backward and exchanges no
+        # gradients between the fold and the optimiser sets it (train.PretrainTrainer); everybody else never stores.
+        self.fold_store = False
+        ParamArena._serial += 1
+        self.fold_key = ("arena", ParamArena._serial)       # context part of ReduceQueue's table-cache key
+        tables = {id(m.weight) for m in module.modules() if isinstance(m, torch.nn.Embedding)}
+        self._fold_ranges = []
+        for o, k, _ in sorted((*self.slices[n], n) for n, p in named if p.dim() >= 2 and id(p) not in tables):
+            if self._fold_ranges and self._fold_ranges[-1][1] == o:
+                self._fold_ranges[-1][1] = o + k
+            else:
+                self._fold_ranges.append([o, o + k])
+        self._fold_starts = [a for a, _ in self._fold_ranges]
+        self._fold_comp = {}
         self.sync_shadow()
         # the compute copy matches the masters as of now: a later write through the parameters (load_state_dict after
         # wrap_model, as map_nav_src/r2r/agent_base.py does; a torch optimiser) moves a version counter and the next
@@ -237,6 +256,106 @@ class ParamArena:
             ops.WgradStream.dirty = False
             ops.WgradStream.release()
 
+    # ---- fused fold: store-mode split-K folds that carry the clip norm (ops.ReduceQueue) --------------------------
+    def store_ok(self, sink_ptr, n):
+        """ReduceQueue's predicate: [sink_ptr, sink_ptr + 4 n) lies inside one range of fold-only parameters."""
+        import bisect
+        off, rem = divmod(sink_ptr - self.grads.data_ptr(), 4)
+        if rem or off < 0 or off + n > self.numel:
+            return False
+        i = bisect.bisect_right(self._fold_starts, off) - 1
+        return i >= 0 and off + n <= self._fold_ranges[i][1]
+
+    def _arm_fold(self):
+        """zero_grad: the arena is zero from here until the backward kernels write it, so the step's first accumulate-flush
+        may store (and carry the clip norm) if the owner allows it; the record of the step before is void."""
+        from . import ops
+        ops.ReduceQueue.store_ok = self.store_ok if self.fold_store else None
+        ops.ReduceQueue.fold_norm = None
+
+    def _name_at(self, sink_ptr):
+        off = (sink_ptr - self.grads.data_ptr()) // 4
+        return next((n for n, (o, k) in self.slices.items() if o <= off < o + k), f"arena offset {off}")
+
+    def fold_check_zero(self, stores):
+        """Warm-up self-check (a): every (sink_ptr, n) about to be STOREd over reads exactly zero."""
+        base = self.grads.data_ptr()
+        views = [self.grads[(p - base) // 4:(p - base) // 4 + n] for p, n in stores]
+        counts = torch.stack([torch.count_nonzero(v) for v in views]).tolist()
+        bad = [(self._name_at(p), c) for (p, _), c in zip(stores, counts) if c]
+        if bad:
+            raise lib.BevBertHipError(
+                "store-mode fold: the gradient of " + ", ".join(f"{n} ({c} non-zero elements)" for n, c in bad[:4])
+                + " is not zero before the step's fold -- something other than the split-K fold writes it, or the arena "
+                "was not zeroed for this step (BEVBERT_FOLD_STORE=0 turns the store mode off)")
+
+    def _fold_complement(self, entry):
+        """(device table, records, bytes) of bevbert_sumsq_tasks over every arena range no NORM task of ``entry`` covers;
+        its slots follow the entry's.  Built in a warm-up step, kept with the arena."""
+        ent = self._fold_comp.get(id(entry))
+        if ent is not None and ent[0] is entry:
+            return ent[1:]
+        if torch.cuda.is_current_stream_capturing():
+            raise lib.BevBertHipError("fold-norm complement table missing during graph capture (warm-up steps build it)")
+        import numpy as np
+        base, recs, pos = self.grads.data_ptr(), [], 0
+        for p, n, _ in sorted(entry["norm_jobs"]) + [(base + 4 * self.numel, 0, 0)]:
+            o = (p - base) // 4
+            for a in range(pos, o, 16384):                  # (tensors start on 1024-element boundaries; n % 4 == 0)
+                recs.append((base + 4 * a, (min(a + 16384, o) - a) // 4))
+            pos = o + n
+            assert pos % 4 == 0, "fold sinks are float4-aligned"
+        from . import ops
+        if entry["nslots"] + len(recs) > ops.ReduceQueue.SLOT_CAPACITY:
+            return None
+        t = np.zeros(len(recs), dtype=np.dtype([("ptr", "<u8"), ("n4", "<u4"), ("slot", "<u4")]))
+        if recs:
+            t["ptr"], t["n4"] = zip(*recs)
+        t["slot"] = entry["nslots"] + np.arange(len(recs))
+        dev = torch.from_numpy(t.view(np.uint8).copy()).to(self.device)
+        if len(self._fold_comp) > 64:
+            self._fold_comp.clear()
+        self._fold_comp[id(entry)] = (entry, dev, len(recs), 16 * int(t["n4"].sum()))
+        return dev, len(recs), 16 * int(t["n4"].sum())
+
+    def _clip_from_fold(self, pre_scale, max_norm):
+        """The fused form of bevbert_grad_norm_clip; False when this step's fold left no record (the caller falls back)."""
+        from . import ops
+        rec, ops.ReduceQueue.fold_norm = ops.ReduceQueue.fold_norm, None         # consumed once
+        if rec is None or rec["owner"] is not self:
+            return False
+        entry = rec["entry"]
+        comp = self._fold_complement(entry)
+        if comp is None:
+            return False
+        table, ntasks, _ = comp
+        slots = ops.ReduceQueue.register_slots(self.device)
+        call("bevbert_sumsq_tasks", table.data_ptr(), ntasks, stream())
+        call("bevbert_clip_from_slots", ptr(slots), entry["nslots"] + ntasks, pre_scale, max_norm, ptr(self._scalars),
+             stream())
+        if entry["fresh"] and not torch.cuda.is_current_stream_capturing():
+            entry["fresh"] = False
+            self._fold_check_norm(entry, slots, pre_scale)
+        return True
+
+    def _fold_check_norm(self, entry, slots, pre_scale):
+        """Warm-up self-check (b), once per table: the fused norm equals the norm of the whole arena to 1e-5."""
+        want = float(torch.linalg.vector_norm(self.grads, dtype=torch.float64)) * pre_scale
+        got = float(self._scalars[0])
+        if abs(got - want) <= 1e-5 * want or (got == 0.0 and want == 0.0):
+            return
+        base, culprit = self.grads.data_ptr(), "a range outside the folds"
+        for p, n, s0 in entry["norm_jobs"]:
+            o = (p - base) // 4
+            w = float(self.grads[o:o + n].double().pow(2).sum())
+            g = float(slots[s0:s0 + (n // 4 + 4095) // 4096].double().sum())
+            if abs(g - w) > 1e-5 * max(w, 1e-30):
+                culprit = self._name_at(p)
+                break
+        raise lib.BevBertHipError(
+            f"fused gradient norm {got!r} differs from the arena's {want!r}: the gradient of {culprit} changed after the "
+            "step's fold (BEVBERT_FOLD_STORE=0 turns the fused norm off)")
+
     def backward_done(self):
         """Call after ``loss.backward()`` when an external loop / optimiser reads the gradients: issues the deferred
         weight-gradient and reduction launches and makes the current stream wait for them (== ``sync``)."""
@@ -250,6 +369,7 @@ class ParamArena:
         if self.device.type == "cuda":
             from . import ops
             ops.RT.scratch.reset()        # partial-sum addresses repeat from step to step (ops.ReduceQueue caches on them)
+            self._arm_fold()
             if overlap:
                 if getattr(self, "_zero_stream", None) is None:
                     from .hwqueues import side_stream
@@ -291,9 +411,13 @@ class ParamArena:
             self.flags.copy_(self._flags_host, non_blocking=True)
             self._flags_dirty = False
 
-    def clip_and_step(self, lr=None, betas=(0.9, 0.98), eps=1e-6, weight_decay=0.01, max_norm=5.0, grad_pre_scale=1.0):
+    def clip_and_step(self, lr=None, betas=(0.9, 0.98), eps=1e-6, weight_decay=0.01, max_norm=5.0, grad_pre_scale=1.0,
+                      fused_norm=False):
         """clip_grad_norm_(max_norm) + AdamW.step (train_r2r.py:295-313) in three launches, no host sync.
-        ``lr=None``: use the device-resident learning rate as set by ``set_lr`` (graph-captured steps)."""
+        ``lr=None``: use the device-resident learning rate as set by ``set_lr`` (graph-captured steps).
+        ``fused_norm``: the caller has not touched ``grads`` since the backward pass that followed ``zero_grad``: when that
+        pass's single fold left its sums of squares behind (ops.ReduceQueue.fold_norm), the norm is taken from them and
+        only the rest of the arena is read; in every other case, and by default, bevbert_grad_norm_clip reads it all."""
         self.sync()
         if self.exp_avg is None:
             self.exp_avg = torch.zeros_like(self.params)
@@ -306,8 +430,10 @@ class ParamArena:
         if not torch.cuda.is_current_stream_capturing():
             self.upload_flags()
         self.step_count += 1
-        call("bevbert_grad_norm_clip", ptr(self.grads), self.numel, float(grad_pre_scale),
-             float(max_norm if max_norm is not None else -1.0), ptr(self._partials), ptr(self._scalars), stream())
+        max_norm = float(max_norm if max_norm is not None else -1.0)
+        if not (fused_norm and self._clip_from_fold(float(grad_pre_scale), max_norm)):
+            call("bevbert_grad_norm_clip", ptr(self.grads), self.numel, float(grad_pre_scale), max_norm,
+                 ptr(self._partials), ptr(self._scalars), stream())
         call("bevbert_adamw_step", ptr(self.params), ptr(self.grads), ptr(self.exp_avg), ptr(self.exp_avg_sq),
              ptr(self.shadow), ptr(self.flags), ptr(self.chunk_steps), self.numel, self._scalars[1:].data_ptr(),
              self._scalars[2:].data_ptr(), 0.0, float(betas[0]), float(betas[1]), float(eps), float(weight_decay),

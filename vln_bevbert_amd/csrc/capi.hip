@@ -45,6 +45,20 @@ BEVBERT_API int bevbert_set_step_salt(const void* device_word) {
   g_step_salt = static_cast<const uint32_t*>(device_word);
   return BB_OK;
 }
+// Slot array of the fused gradient norm (bevbert_multi_accum's NORM tasks, bevbert_sumsq_tasks): like the salt, a pointer
+// read on the host at launch time and passed to the kernel as an argument.
+static float* g_fold_norm_slots = nullptr;
+static int g_fold_norm_capacity = 0;
+float* bb_fold_norm_slots(int* capacity) {
+  *capacity = g_fold_norm_capacity;
+  return g_fold_norm_slots;
+}
+BEVBERT_API int bevbert_set_fold_norm_slots(float* slots, int capacity) {
+  BB_REQUIRE(capacity >= 0 && capacity <= (1 << 20), "set_fold_norm_slots: capacity %d outside [0, 2^20]", capacity);
+  g_fold_norm_slots = capacity > 0 ? slots : nullptr;
+  g_fold_norm_capacity = g_fold_norm_slots ? capacity : 0;
+  return BB_OK;
+}
 BEVBERT_API const char* bevbert_arch(void) { return "gfx950"; }
 
 int attn_simple_fwd(const AttnArgs& a, int dtype, hipStream_t st);

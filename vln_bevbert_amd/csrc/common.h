@@ -226,6 +226,8 @@ __host__ __device__ __forceinline__ uint32_t bb_drop_threshold(float p) {
 // every training step (a 4-byte fill on the stream); every dropout kernel then uses hash(key ^ *salt) instead of key,
 // so a replayed graph draws fresh masks and forward / backward of one step still agree.  No salt registered: key as is.
 const uint32_t* bb_step_salt();
+// the slot array registered with bevbert_set_fold_norm_slots (NULL, capacity 0: none)
+float* bb_fold_norm_slots(int* capacity);
 __device__ __forceinline__ uint32_t bb_salted(uint32_t key, const uint32_t* __restrict__ salt) {
   return salt ? bb_hash32(key ^ *salt) : key;
 }

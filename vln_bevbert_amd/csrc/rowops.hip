@@ -667,21 +667,27 @@ __global__ __launch_bounds__(192) void gather_wsum_kernel(const T* __restrict__ 
 // task record is otherwise a flat one, and the store of one element would fence the loads of the next).  The adds of an
 // element stay ((sink + p0) + p1) + ... + p(S-1), whatever S: slices beyond the last full batch are taken one at a time
 // in the same order.  Elements past the end are clamped to the last one for the loads and not stored.
+// STORE (a task flag of bevbert_multi_accum): the caller knows the sink range to be zero (the arena fill, nothing added
+// since), so the chain starts from 0.f -- ((0 + p0) + p1) + ..., the same bits -- and the sink is never loaded: a third of
+// the fold's bytes at fp32 S = 1, a quarter at bf16 S = 4.  The return value is the thread's sum of squares of what it stored, in
+// the order it stored it (clamped duplicates not counted): the fused gradient norm of the NORM flag.
 #define ACCUM_U 4
 #define ACCUM_SC 4
-// sink[i] += sum_s part[s * stride4 + i] for the float4 groups i = first, first + step, ... < n4
-template <typename T>
-__device__ __forceinline__ void accum_fold(const T* part_, float* sink_, size_t stride4, size_t n4, int S, size_t first,
-                                           size_t step) {
+// sink[i] (+)= sum_s part[s * stride4 + i] for the float4 groups i = first, first + step, ... < n4
+template <typename T, bool STORE = false>
+__device__ __forceinline__ float accum_fold(const T* part_, float* sink_, size_t stride4, size_t n4, int S, size_t first,
+                                            size_t step) {
   const BB_GLOBAL T* __restrict__ part = (const BB_GLOBAL T*)part_;
   BB_GLOBAL float* __restrict__ sink = (BB_GLOBAL float*)sink_;
+  float sq = 0.f;
   for (size_t i = first; i < n4; i += ACCUM_U * step) {
     size_t idx[ACCUM_U];
     float4 acc[ACCUM_U];
 #pragma unroll
     for (int u = 0; u < ACCUM_U; ++u) {
       idx[u] = i + u * step < n4 ? i + u * step : n4 - 1;
-      acc[u] = gld4<float>(sink + idx[u] * 4);
+      if constexpr (STORE) acc[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+      else acc[u] = gld4<float>(sink + idx[u] * 4);
     }
     int s = 0;
     for (; s + ACCUM_SC <= S; s += ACCUM_SC) {
@@ -707,8 +713,10 @@ __device__ __forceinline__ void accum_fold(const T* part_, float* sink_, size_t 
       if (i + u * step < n4) {
         const bb_f4v o = {acc[u].x, acc[u].y, acc[u].z, acc[u].w};
         *reinterpret_cast<BB_GLOBAL bb_f4v*>(sink + idx[u] * 4) = o;
+        sq += (acc[u].x * acc[u].x + acc[u].y * acc[u].y) + (acc[u].z * acc[u].z + acc[u].w * acc[u].w);
       }
   }
+  return sq;
 }
 
 template <typename T>
@@ -725,16 +733,37 @@ struct AccumTask {
   float* sink;             // this task's first element in the arena
   unsigned long long n4_total;   // stride between the S partial slices, in float4 groups
   unsigned int off4, n4;   // range of this task inside a slice, in float4 groups
-  int S, dtype;            // dtype: BB_F32 / BB_BF16
+  int S, dtype;            // dtype: bits 0-7 BB_F32 / BB_BF16, bit 8 STORE, bit 9 NORM, bits 12-31 the NORM slot
 };
-template <typename T>
-__device__ __forceinline__ void accum_task(const AccumTask& t) {
-  accum_fold<T>((const T*)t.partials + (size_t)t.off4 * 4, t.sink, t.n4_total, t.n4, t.S, threadIdx.x, 256);
+#define ACCUM_STORE 0x100
+#define ACCUM_NORM 0x200
+// sum of the 256 threads' values, in the fixed order of sumsq_kernel; the result is valid in thread 0
+__device__ __forceinline__ float block_sum_256(float s) {
+  __shared__ float sh[4];
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+  __syncthreads();
+  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
-__global__ __launch_bounds__(256) void multi_accum_kernel(const AccumTask* __restrict__ tasks) {
+template <typename T, bool STORE>
+__device__ __forceinline__ float accum_task(const AccumTask& t) {
+  return accum_fold<T, STORE>((const T*)t.partials + (size_t)t.off4 * 4, t.sink, t.n4_total, t.n4, t.S, threadIdx.x, 256);
+}
+// NORM: slots[slot] = sum of squares of the task's stored values -- one writer per slot, no atomics; the optimiser sums
+// the slots (clip_from_slots) instead of reading the arena again.  Ignored without a registered slot array
+// (bevbert_set_fold_norm_slots) or with a slot beyond its capacity.
+__global__ __launch_bounds__(256) void multi_accum_kernel(const AccumTask* __restrict__ tasks, float* __restrict__ slots,
+                                                          unsigned int capacity) {
   const AccumTask t = tasks[blockIdx.x];
-  if (t.dtype == BB_BF16) accum_task<bf16_raw>(t);
-  else accum_task<float>(t);
+  const bool bf16 = (t.dtype & 0xff) == BB_BF16;
+  float sq;
+  if (t.dtype & ACCUM_STORE) sq = bf16 ? accum_task<bf16_raw, true>(t) : accum_task<float, true>(t);
+  else sq = bf16 ? accum_task<bf16_raw, false>(t) : accum_task<float, false>(t);
+  const unsigned int slot = (unsigned int)t.dtype >> 12;
+  if ((t.dtype & ACCUM_NORM) && slot < capacity) {       // block-uniform: the barrier inside is reached by all or none
+    sq = block_sum_256(sq);
+    if (threadIdx.x == 0) slots[slot] = sq;
+  }
 }
 
 // table_grad[t] += sum of d[r] over the rows r with ids[r] == t, WITHOUT atomics and in a fixed order (training runs are
@@ -859,6 +888,34 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) partials[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+// Sum of squares of the arena ranges no NORM fold covers (embedding tables, biases, LayerNorm vectors, padding): one
+// block per record {ptr, n4 <= 4096 float4 groups, slot}, every load of a thread issued before its adds.
+struct SumsqTask {
+  const float* ptr;
+  unsigned int n4, slot;
+};
+__global__ __launch_bounds__(256) void sumsq_tasks_kernel(const SumsqTask* __restrict__ tasks, float* __restrict__ slots,
+                                                          unsigned int capacity) {
+  const SumsqTask t = tasks[blockIdx.x];
+  if (t.slot >= capacity) return;                        // block-uniform
+  const unsigned int n4 = t.n4 < 4096u ? t.n4 : 4096u;
+  float s = 0.f;
+  if (n4) {
+    const BB_GLOBAL float* __restrict__ g = (const BB_GLOBAL float*)t.ptr;
+    float4 v[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const unsigned int i = threadIdx.x + u * 256;
+      v[u] = gld4<float>(g + (size_t)(i < n4 ? i : n4 - 1) * 4);
+    }
+#pragma unroll
+    for (int u = 0; u < 16; ++u)
+      if (threadIdx.x + u * 256 < n4) s += (v[u].x * v[u].x + v[u].y * v[u].y) + (v[u].z * v[u].z + v[u].w * v[u].w);
+  }
+  s = block_sum_256(s);
+  if (threadIdx.x == 0) slots[t.slot] = s;
 }
 
 // scalars[0] = total L2 norm of (pre_scale * g) ; scalars[1] = multiplier the optimiser applies to g:
@@ -1519,12 +1576,31 @@ BEVBERT_API int bevbert_colsum_partials(const void* dy, float* partials, int row
 }
 
 // tasks: device array of `ntasks` 40-byte records {u64 partials, u64 sink, u64 n4_total, u32 off4, u32 n4, i32 S, i32 dtype}
+// dtype: bits 0-7 the dtype code, bit 8 STORE (the sink range is known to be zero: not read), bit 9 NORM (the task's sum
+// of squares goes to slot `dtype >> 12` of the array registered with bevbert_set_fold_norm_slots); both zero: as before.
 BEVBERT_API int bevbert_multi_accum(const void* tasks, int ntasks, hipStream_t stream) {
   static_assert(sizeof(AccumTask) == 40, "AccumTask is part of the C ABI");
   if (ntasks <= 0) return BB_OK;
   BB_REQUIRE(tasks != nullptr, "multi_accum: null task table");
-  hipLaunchKernelGGL(multi_accum_kernel, dim3(ntasks), dim3(256), 0, stream, (const AccumTask*)tasks);
+  int capacity = 0;
+  float* slots = bb_fold_norm_slots(&capacity);
+  hipLaunchKernelGGL(multi_accum_kernel, dim3(ntasks), dim3(256), 0, stream, (const AccumTask*)tasks, slots,
+                     (unsigned int)(slots ? capacity : 0));
   BB_CHECK_LAUNCH("multi_accum");
+  return BB_OK;
+}
+
+// tasks: device array of `ntasks` 16-byte records {u64 ptr, u32 n4 <= 4096, u32 slot}: slots[slot] = sum of squares of the
+// n4 float4 groups at ptr (slots: the array registered with bevbert_set_fold_norm_slots)
+BEVBERT_API int bevbert_sumsq_tasks(const void* tasks, int ntasks, hipStream_t stream) {
+  static_assert(sizeof(SumsqTask) == 16, "SumsqTask is part of the C ABI");
+  if (ntasks <= 0) return BB_OK;
+  int capacity = 0;
+  float* slots = bb_fold_norm_slots(&capacity);
+  BB_REQUIRE(tasks != nullptr && slots != nullptr, "sumsq_tasks: null task table, or no slot array registered");
+  hipLaunchKernelGGL(sumsq_tasks_kernel, dim3(ntasks), dim3(256), 0, stream, (const SumsqTask*)tasks, slots,
+                     (unsigned int)capacity);
+  BB_CHECK_LAUNCH("sumsq_tasks");
   return BB_OK;
 }
 
@@ -1634,6 +1710,16 @@ BEVBERT_API int bevbert_grad_norm_clip(const float* grads, int64_t n, float pre_
   hipLaunchKernelGGL(sumsq_kernel, dim3(1024), dim3(256), 0, stream, grads, (size_t)n / 4, partials);
   hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(256), 0, stream, partials, 1024, pre_scale, max_norm, scalars);
   BB_CHECK_LAUNCH("grad_norm_clip");
+  return BB_OK;
+}
+
+// bevbert_grad_norm_clip's second half over `n` per-task sums of squares (NORM folds + bevbert_sumsq_tasks): fp64 sum in a
+// fixed order, the same scalars[0..1]
+BEVBERT_API int bevbert_clip_from_slots(const float* slots, int n, float pre_scale, float max_norm, float* scalars,
+                                        hipStream_t stream) {
+  BB_REQUIRE(n >= 0 && (slots != nullptr || n == 0) && scalars != nullptr, "clip_from_slots: null pointer or negative count");
+  hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(256), 0, stream, slots, n, pre_scale, max_norm, scalars);
+  BB_CHECK_LAUNCH("clip_from_slots");
   return BB_OK;
 }
 

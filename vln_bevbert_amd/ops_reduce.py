@@ -272,6 +272,33 @@ class ReduceQueue:
     _accum_tables = {}
     _dtype = None
     _adtype = None
+    # Fused fold (task flags of bevbert_multi_accum, include/bevbert_hip.h).  ``store_ok``: predicate on (sink_ptr, n) that
+    # says "this range of the gradient arena was zeroed for this step and only split-K folds write it"; None (the default:
+    # ops used without an arena, every caller that does not zero per step) means never.  ParamArena.zero_grad arms it, the
+    # step's FIRST accumulate-flush consumes it: a sink's round-0 task then STOREs (starts from 0.f, does not read the
+    # sink) and the tasks of its last round leave their sums of squares in ``_slots`` (NORM).  ``fold_norm`` is the record
+    # that flush leaves for ParamArena.clip_and_step; any further accumulate-flush builds plain tables and clears it.
+    FOLD_STORE = _os.environ.get("BEVBERT_FOLD_STORE", "1") == "1"      # A/B knob
+    STORE, NORM = 0x100, 0x200
+    SLOT_CAPACITY = 1 << 16      # one float per 16 384-element task: arenas of up to ~1 G elements
+    store_ok = None
+    fold_norm = None
+    _slots = None
+
+    @classmethod
+    def slots(cls, device):
+        """The process-wide slot array of the fused gradient norm (allocated by the first table that needs it)."""
+        if cls._slots is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise lib.BevBertHipError("fold-norm slot array missing during graph capture (warm-up steps allocate it)")
+            cls._slots = torch.zeros(cls.SLOT_CAPACITY, dtype=torch.float32, device=device)
+        return cls._slots
+
+    @classmethod
+    def register_slots(cls, device):
+        s = cls.slots(device)
+        lib.load().bevbert_set_fold_norm_slots(s.data_ptr(), s.numel())
+        return s
 
     @classmethod
     def _note_producer(cls):
@@ -306,13 +333,16 @@ class ReduceQueue:
         cls._note_producer()
 
     @classmethod
-    def _build_accum(cls, jobs, device):
+    def _build_accum(cls, jobs, device, flags=None, slot0=0):
+        """Device task table of ``jobs``.  ``flags``: per job, STORE | NORM bits (None: a plain accumulate table); the NORM
+        tasks take the slots slot0, slot0 + 1, ... in table order."""
         import numpy as np
         if cls._adtype is None:
             cls._adtype = np.dtype([("partials", "<u8"), ("sink", "<u8"), ("n4_total", "<u8"), ("off4", "<u4"),
                                     ("n4", "<u4"), ("S", "<i4"), ("dtype", "<i4")])
-        parts = []
-        for partials_ptr, sink_ptr, S, n, dt in jobs:
+        parts, slot = [], slot0
+        flags = flags if flags is not None else [0] * len(jobs)
+        for (partials_ptr, sink_ptr, S, n, dt), fl in zip(jobs, flags):
             n4 = n // 4
             off = np.arange(0, n4, 4096, dtype=np.int64)
             t = np.zeros(len(off), dtype=cls._adtype)
@@ -322,13 +352,50 @@ class ReduceQueue:
             t["off4"] = off
             t["n4"] = np.minimum(4096, n4 - off)
             t["S"] = S
-            t["dtype"] = dt
+            word = np.full(len(off), dt | (fl & (cls.STORE | cls.NORM)), dtype=np.int64)
+            if fl & cls.NORM:
+                word |= (slot + np.arange(len(off), dtype=np.int64)) << 12
+                slot += len(off)
+            t["dtype"] = word.astype(np.uint32).view(np.int32)
             parts.append(t)
         table = np.concatenate(parts) if parts else np.zeros(0, dtype=cls._adtype)
         dev = torch.from_numpy(table.view(np.uint8).copy()).to(device)
-        # every partial slice read once (its own dtype), the sink read and written once (fp32)
-        cls.table_bytes[dev.data_ptr()] = int(sum(S * n * (4 if dt == lib.F32 else 2) + 8 * n for _, _, S, n, dt in jobs))
+        # every partial slice read once (its own dtype), the sink written once and -- unless the task stores -- read once
+        cls.table_bytes[dev.data_ptr()] = int(sum(S * n * (4 if dt == lib.F32 else 2) + (4 * n if fl & cls.STORE else 8 * n)
+                                                  for (_, _, S, n, dt), fl in zip(jobs, flags)))
         return dev, len(table)
+
+    @classmethod
+    def _plan_fold(cls, jobs, ok):
+        """rounds [[job]], flags [[int]] of an accumulate job list.  A weight used twice in one backward goes into
+        successive launches (as ever).  With a predicate ``ok``, a sink it accepts STOREs in its round-0 task and takes
+        its NORM from the tasks of its last round; a sink whose jobs disagree about its length, or whose range overlaps
+        another sink's, is left to plain accumulation."""
+        rounds, seen, last = [[]], [set()], {}
+        for job in jobs:
+            r = 0
+            while job[1] in seen[r]:
+                r += 1
+                if r == len(rounds):
+                    rounds.append([])
+                    seen.append(set())
+            rounds[r].append(job)
+            seen[r].add(job[1])
+            last[job[1]] = r
+        if ok is None:
+            return rounds, [[0] * len(r) for r in rounds]
+        lengths = {}
+        for job in jobs:
+            lengths.setdefault(job[1], set()).add(job[3])
+        spans = sorted((p, p + 4 * max(ns)) for p, ns in lengths.items())
+        clash = set()
+        for (p0, e0), (p1, _) in zip(spans, spans[1:]):
+            if e0 > p1:
+                clash |= {p0, p1}
+        good = {p for p, ns in lengths.items() if len(ns) == 1 and p not in clash and ok(p, next(iter(ns)))}
+        flags = [[(cls.STORE if r == 0 and j[1] in good else 0) | (cls.NORM if j[1] in good and last[j[1]] == r else 0)
+                  for j in rnd] for r, rnd in enumerate(rounds)]
+        return rounds, flags
 
     @classmethod
     def add(cls, partials_ptr, nblocks, nwhich, C, outs, accumulate=1):
@@ -370,27 +437,46 @@ class ReduceQueue:
         into the SAME output vector (a parameter used twice in one backward: REVERIE's object tokens share
         img_linear / img_layer_norm with the views) must not run concurrently: they go into successive launches."""
         if cls.accum_jobs:
-            akey = tuple(cls.accum_jobs)
+            jobs = tuple(cls.accum_jobs)
             cls.accum_jobs = []
+            # the step's first accumulate-flush consumes the store context; a further one (early flush, the reducer's
+            # launches) finds none, builds plain accumulate tables and disarms the fused norm of this step
+            ok, cls.store_ok, cls.fold_norm = (cls.store_ok if cls.FOLD_STORE else None), None, None
+            owner = getattr(ok, "__self__", ok)
+            akey = (jobs, None if ok is None else getattr(owner, "fold_key", id(owner)))
             aent = cls._accum_tables.get(akey)
             if aent is None:
                 if torch.cuda.is_current_stream_capturing():
                     raise lib.BevBertHipError("accumulate task table missing during graph capture (warm-up steps build it)")
                 if len(cls._accum_tables) > 256:
                     cls._accum_tables.clear()
-                rounds, seen = [[]], [set()]
-                for job in akey:                      # a weight used twice in one backward: successive launches
-                    r = 0
-                    while job[1] in seen[r]:
-                        r += 1
-                        if r == len(rounds):
-                            rounds.append([])
-                            seen.append(set())
-                    rounds[r].append(job)
-                    seen[r].add(job[1])
-                aent = cls._accum_tables[akey] = [cls._build_accum(tuple(r), device) for r in rounds]
-            for table, n in aent:
+                rounds, flags = cls._plan_fold(jobs, ok)
+                tasks_of = lambda j: (j[3] // 4 + 4095) // 4096
+                n_norm = sum(tasks_of(j) for rnd, fl in zip(rounds, flags) for j, f in zip(rnd, fl) if f & cls.NORM)
+                if n_norm > cls.SLOT_CAPACITY // 2:                               # (an arena beyond the slot array's reach)
+                    flags = [[f & ~cls.NORM for f in fl] for fl in flags]
+                tables, nslots, norm_jobs = [], 0, []
+                for rnd, fl in zip(rounds, flags):
+                    tables.append(cls._build_accum(tuple(rnd), device, fl, nslots))
+                    for j, f in zip(rnd, fl):
+                        if f & cls.NORM:
+                            norm_jobs.append((j[1], j[3], nslots))                 # sink, elements, first slot
+                            nslots += tasks_of(j)
+                aent = {
+                    "tables": tables, "nslots": nslots, "norm_jobs": norm_jobs, "fresh": True,
+                    "flagged": any(f for fl in flags for f in fl),
+                    "stores": [(j[1], j[3]) for rnd, fl in zip(rounds, flags) for j, f in zip(rnd, fl) if f & cls.STORE]}
+                if aent["stores"] and hasattr(owner, "fold_check_zero"):
+                    # self-check of the warm-up steps (a table is never built inside a capture): what is about to be
+                    # stored over must read zero now -- an unknown writer is an error here, not a lost gradient in replay
+                    _on_launch_stream(lambda: owner.fold_check_zero(aent["stores"]))
+                cls._accum_tables[akey] = aent
+            if aent["flagged"]:
+                cls.register_slots(device)
+            for table, n in aent["tables"]:
                 call("bevbert_multi_accum", table.data_ptr(), n, stream())
+            if aent["nslots"]:
+                cls.fold_norm = {"owner": owner, "entry": aent}
         if not cls.jobs:
             return
         key = tuple(cls.jobs)

@@ -285,6 +285,12 @@ class GradReducer:
         self._done = []
 
 
+def fold_store_allowed(device_type, reducer_active, early_flush, env=None):
+    """May the step's fold store and carry the clip norm (PretrainTrainer.__init__ explains the conditions)?"""
+    env = os.environ if env is None else env
+    return env.get("BEVBERT_FOLD_STORE", "1") == "1" and device_type == "cuda" and not reducer_active and not early_flush
+
+
 class PretrainTrainer:
     def __init__(self, model, arena, learning_rate=5e-5, warmup_steps=10000, num_train_steps=100000,
                  betas=(0.9, 0.98), weight_decay=0.01, grad_norm=5.0, seed=0, rank=0, world_size=1, overlap=True,
@@ -333,6 +339,11 @@ class PretrainTrainer:
         self.early_flush = os.environ.get("BEVBERT_EARLY_FLUSH", "0") == "1" and arena.device.type == "cuda"
         if self.early_flush and not self.overlap:
             model.bert.lang_encoder.register_forward_hook(self._hook_flush)
+        # Store-mode folds that carry the clip norm (ops.ReduceQueue, ParamArena.store_ok): this trainer zeroes the arena
+        # before every backward pass, so the step's single fold may start from 0.f instead of reading the zeros back.  Not
+        # with a gradient exchange (the all-reduce changes the gradients after the fold: the norm must be taken afterwards)
+        # nor with the early flush (two folds per step).  BEVBERT_FOLD_STORE=0 turns it off (A/B).
+        arena.fold_store = fold_store_allowed(arena.device.type, self.reducer.active, self.early_flush)
         if self.overlap:
             self.install_map_layer_hooks()
             model.bert.lang_encoder.register_forward_hook(self._hook_text)
@@ -497,12 +508,14 @@ class PretrainTrainer:
         self.reducer.finish()
         return loss.detach()
 
-    def optimizer_step(self, lr=None):
+    def optimizer_step(self, lr=None, fused_norm=False):
         """clip_grad_norm_ + AdamW + schedule (train_r2r.py:278-313) on the flat arena.  ``lr=None``: the schedule value
-        of the current global step is computed here and written to the device-resident slot."""
+        of the current global step is computed here and written to the device-resident slot.  ``fused_norm``: see
+        ParamArena.clip_and_step -- ``step`` passes it, a caller that may have edited ``arena.grads`` does not."""
         if lr is None:
             lr = warmup_linear_lr(self.global_step, self.lr, self.warmup, self.total)
-        self.arena.clip_and_step(lr, self.betas, 1e-6, self.wd, self.grad_norm, grad_pre_scale=1.0 / self.world)
+        self.arena.clip_and_step(lr, self.betas, 1e-6, self.wd, self.grad_norm, grad_pre_scale=1.0 / self.world,
+                                 fused_norm=fused_norm)
 
     def step(self, task, batch):
         """One optimisation step on one batch (gradient_accumulation_steps == 1, as every shipped config).
@@ -513,7 +526,7 @@ class PretrainTrainer:
         if isinstance(batch, StaticBatch) and self.use_graphs and self.capture_ok and batch.capturable and ops.RT.trace is None:
             return self._static_step(task, batch)
         loss = self.forward_backward(task, batch)
-        self.optimizer_step()
+        self.optimizer_step(fused_norm=True)
         return loss
 
     def validate(self, val_loaders, setname="", **kw):
@@ -552,7 +565,7 @@ class PretrainTrainer:
                 loss = self._forward_backward(task, sb)
             finally:
                 ops.Branches.enabled = branches
-            self.optimizer_step(lr=None)
+            self.optimizer_step(lr=None, fused_norm=True)
             return loss
         # capture: flags / plans / side streams are warm, nothing below allocates outside the graph's pool
         a.upload_flags()
@@ -582,7 +595,8 @@ class PretrainTrainer:
                     # attention site is captured as a side branch of the graph (ops.ATTN_BITS)
                     ops.RT.new_step(0, write_salt=False, plan_key=self._plan_key(task, sb))
                     loss = self._forward_backward(task, sb)
-                    a.clip_and_step(None, self.betas, 1e-6, self.wd, self.grad_norm, grad_pre_scale=1.0 / self.world)
+                    a.clip_and_step(None, self.betas, 1e-6, self.wd, self.grad_norm, grad_pre_scale=1.0 / self.world,
+                                    fused_norm=True)
                 except Exception as e:      # noqa: BLE001 -- still inside the capture: join the forked side streams so that
                     err = e                 # the capture can END (an unjoined capture stays open on this ROCm, see ops)
                     ops.join_captured_side_streams(extra=[self.reducer.stream])
@@ -610,7 +624,7 @@ class PretrainTrainer:
             self.reducer.drop_pending()
             ops.RT.new_step(self._step_seed(), plan_key=self._plan_key(task, sb))
             loss = self._forward_backward(task, sb)
-            self.optimizer_step(lr=None)
+            self.optimizer_step(lr=None, fused_norm=True)
             return loss
         ops.Branches.enabled = branches
         gs = GraphedStep(graph, loss)
