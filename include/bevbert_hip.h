@@ -159,6 +159,15 @@ int bevbert_layernorm_res32_fwd(const void* x, const float* bias, const void* re
                                 const float* gamma, const float* beta, void* y16, float* y32, float* z32, float* mean,
                                 float* rstd, int rows, int H, float eps, float drop_p, uint64_t seed, uint64_t offset,
                                 hipStream_t stream);
+/* bevbert_layernorm_res32_fwd for a residual that is the fp32 output of the PREVIOUS LayerNorm of the stream, when that
+ * call wrote no y32 (since 0.3.0; entry point added, ABI otherwise unchanged): the residual is recomputed as
+ * (z_prev - mean_prev) * rstd_prev * gamma_prev + beta_prev from the previous call's z32, mean, rstd (all required, fp32)
+ * and its gamma / beta, with the arithmetic that call would have used for its y32 -- bit for bit the same results. */
+int bevbert_layernorm_res32_chain_fwd(const void* x, const float* bias, const float* z_prev, const float* mean_prev,
+                                      const float* rstd_prev, const float* gamma_prev, const float* beta_prev,
+                                      const float* gamma, const float* beta, void* y16, float* y32, float* z32,
+                                      float* mean, float* rstd, int rows, int H, float eps, float drop_p, uint64_t seed,
+                                      uint64_t offset, hipStream_t stream);
 int bevbert_layernorm_res32_bwd(const void* dy16, const float* dy32, const float* z32, const float* mean,
                                 const float* rstd, const float* gamma, void* dz, void* dx16, float* dgamma,
                                 float* dbeta, float* dbias, float* workspace, int rows, int H, float drop_p, uint64_t seed,

@@ -73,6 +73,12 @@ def main():
                                     ptr(y32), ptr(z32), ptr(mean), ptr(rstd), rows, H, 1e-12, p, 1, 0, stream()))
             nb = rows * H * (2 + 4 + 2 + 4 + 4)
             print(json.dumps({"kernel": "ln_res32_fwd", "rows": rows, "p": p, "us": round(t, 2), "bytes": nb, "mark": _mark_idx[0], "GBps": round(nb / t / 1e3, 1)}), flush=True)
+            # the chained form in the middle of a stream: the producer's z32 / mean / rstd in (r32, mean2, rstd2 stand in), no y32 out
+            mean2, rstd2 = torch.randn(rows, device=dev), torch.rand(rows, device=dev) + 0.5
+            t = timeit(lambda: call("bevbert_layernorm_res32_chain_fwd", ptr(x), ptr(bias), ptr(r32), ptr(mean2), ptr(rstd2), ptr(gamma),
+                                    ptr(beta), ptr(gamma), ptr(beta), ptr(y), None, ptr(z32), ptr(mean), ptr(rstd), rows, H, 1e-12, p, 1, 0, stream()))
+            nb = rows * H * (2 + 4 + 2 + 4)
+            print(json.dumps({"kernel": "ln_res32_chain_fwd", "rows": rows, "p": p, "us": round(t, 2), "bytes": nb, "mark": _mark_idx[0], "GBps": round(nb / t / 1e3, 1)}), flush=True)
             t = timeit(lambda: call("bevbert_layernorm_res32_bwd", ptr(dy), ptr(dy32), ptr(z32), ptr(mean), ptr(rstd), ptr(gamma),
                                     ptr(dz32), ptr(dx), None, None, None, ptr(ws), rows, H, p, 1, 0, 0, 0, stream()))
             nb = rows * H * (2 + 4 + 4 + 4 + 2)

@@ -242,15 +242,26 @@ __device__ __forceinline__ void walk_rows_ahead(int row, int rows, int stride, F
 //   backward: dy = dy16 (bf16: from the GEMMs that read y16) + dy32 (fp32: from the residual add that read y32), either
 //             may be null; dz32 (fp32) continues the residual stream's gradient, dx16 = bf16(dz through the dropout mask)
 //             feeds the dense layer's backward GEMMs; column partials as in ln_bwd_kernel
+//   CHAIN:    the residual is the fp32 output of the PREVIOUS LayerNorm of the stream, which that launch did not write:
+//             `residual` is its saved pre-norm sum z32 and the chunk is ln_norm4 of it with that launch's mean, rstd, gamma
+//             and beta -- the producer's own expression on the producer's own fp32 operands, hence its bits.  The stream
+//             then costs 12 B per element and launch (x, z_prev in; y16, z32 out) instead of 16.
 // =============================================================================================
-template <typename TR, int NV>
-__global__ __launch_bounds__(256) void ln_res32_fwd_kernel(const bf16_raw* __restrict__ x, const float* __restrict__ bias,
+struct LnPrev { const float* mean; const float* rstd; const float* gamma; const float* beta; };   // CHAIN: of the producer
+
+// (eight waves per SIMD, i.e. at most 64 VGPRs: what the plain forms take anyway, while the chained one at H = 768 would
+// otherwise keep every chunk's operands in flight at once -- 66 VGPRs, seven waves; at H = 1 024 it would need 82 and
+// spills under 64, so there it is left six waves)
+template <typename TR, int NV, bool CHAIN>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CHAIN && NV == 4 ? 6 : 8, 8))) void ln_res32_fwd_kernel(const bf16_raw* __restrict__ x, const float* __restrict__ bias,
                                                            const TR* __restrict__ residual, const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, bf16_raw* __restrict__ y16,
                                                            float* __restrict__ y32, float* __restrict__ z_out,
                                                            float* __restrict__ mean_out, float* __restrict__ rstd_out,
                                                            int rows, float eps, float drop_p, uint32_t drop_thr,
-                                                           uint32_t drop_key, const uint32_t* __restrict__ salt) {
+                                                           uint32_t drop_key, const uint32_t* __restrict__ salt,
+                                                           const LnPrev prev) {
+  static_assert(!CHAIN || std::is_same<TR, float>::value, "a chained residual is the producer's fp32 z");
   constexpr int H = NV * 256;
   if (drop_p > 0.f) drop_key = bb_salted(drop_key, salt);
   const int lane = threadIdx.x & 63;
@@ -258,12 +269,18 @@ __global__ __launch_bounds__(256) void ln_res32_fwd_kernel(const bf16_raw* __res
   if (row >= rows) return;
   float4 v[NV];
   const float keep_scale = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
+  float mean_prev = 0.f, rstd_prev = 0.f;
+  if (CHAIN) {
+    mean_prev = prev.mean[row];
+    rstd_prev = prev.rstd[row];
+  }
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int col = (i * 64 + lane) * 4;
     const float4 a = ld4<bf16_raw>(x + (size_t)row * H + col);
-    const bool has_res = residual != nullptr;
-    const float4 r = has_res ? ld4<TR>(residual + (size_t)row * H + col) : make_float4(0.f, 0.f, 0.f, 0.f);
+    const bool has_res = CHAIN || residual != nullptr;
+    float4 r = has_res ? ld4<TR>(residual + (size_t)row * H + col) : make_float4(0.f, 0.f, 0.f, 0.f);
+    if (CHAIN) r = ln_norm4(r, mean_prev, rstd_prev, prev.gamma, prev.beta, col);
     v[i] = ln_fwd_input(a, bias, col, drop_p, (uint32_t)row * H + col, drop_key, drop_thr, keep_scale, has_res, r);
   }
   // ln_row_stats written out, for the reason given in ln_fwd_kernel
@@ -1445,12 +1462,35 @@ BEVBERT_API int bevbert_layernorm_res32_fwd(const void* x, const float* bias, co
   bb_with_type(residual != nullptr && residual_dtype == BB_BF16 ? BB_BF16 : BB_F32, [&](auto t) {
     using TR = decltype(t);
     bb_with_width<1, 2, 3, 4>(H, [&](auto nv) {
-      hipLaunchKernelGGL((ln_res32_fwd_kernel<TR, decltype(nv)::value>), grid, dim3(256), 0, stream, (const bf16_raw*)x, bias,
-                         (const TR*)residual, gamma, beta, (bf16_raw*)y16, y32, z32, mean, rstd, rows, eps, drop_p, thr,
-                         bb_site_key(seed, offset), bb_step_salt());
+      hipLaunchKernelGGL((ln_res32_fwd_kernel<TR, decltype(nv)::value, false>), grid, dim3(256), 0, stream, (const bf16_raw*)x,
+                         bias, (const TR*)residual, gamma, beta, (bf16_raw*)y16, y32, z32, mean, rstd, rows, eps, drop_p, thr,
+                         bb_site_key(seed, offset), bb_step_salt(), LnPrev{});
     });
   });
   BB_CHECK_LAUNCH("layernorm_res32_fwd");
+  return BB_OK;
+}
+
+// The same where the residual is the previous LayerNorm's fp32 output and that launch wrote no y32: the kernel recomputes
+// it from what the producer saved for its own backward (z_prev, mean_prev, rstd_prev) and the producer's gamma / beta.
+BEVBERT_API int bevbert_layernorm_res32_chain_fwd(const void* x, const float* bias, const float* z_prev,
+                                                  const float* mean_prev, const float* rstd_prev, const float* gamma_prev,
+                                                  const float* beta_prev, const float* gamma, const float* beta, void* y16,
+                                                  float* y32, float* z32, float* mean, float* rstd, int rows, int H,
+                                                  float eps, float drop_p, uint64_t seed, uint64_t offset,
+                                                  hipStream_t stream) {
+  BB_REQUIRE(rows >= 0 && H >= 256 && H % 256 == 0 && H / 256 <= 4, "layernorm_res32_chain_fwd: H=%d must be 256, 512, 768 or 1024", H);
+  BB_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "layernorm_res32_chain_fwd: dropout p=%f", drop_p);
+  if (rows == 0) return BB_OK;
+  BB_REQUIRE(z_prev && mean_prev && rstd_prev && gamma_prev && beta_prev, "layernorm_res32_chain_fwd: %s", "the producer's z, mean, rstd, gamma and beta are all required");
+  const dim3 grid((rows + 3) / 4);
+  const uint32_t thr = bb_drop_threshold(drop_p);
+  bb_with_width<1, 2, 3, 4>(H, [&](auto nv) {
+    hipLaunchKernelGGL((ln_res32_fwd_kernel<float, decltype(nv)::value, true>), grid, dim3(256), 0, stream, (const bf16_raw*)x,
+                       bias, z_prev, gamma, beta, (bf16_raw*)y16, y32, z32, mean, rstd, rows, eps, drop_p, thr,
+                       bb_site_key(seed, offset), bb_step_salt(), LnPrev{mean_prev, rstd_prev, gamma_prev, beta_prev});
+  });
+  BB_CHECK_LAUNCH("layernorm_res32_chain_fwd");
   return BB_OK;
 }
 

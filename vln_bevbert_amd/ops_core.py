@@ -237,7 +237,8 @@ class Branches:
 # that a caller (a test, bench.py) that swaps them reaches every module of the package.
 
 
-_ROWS_ARG = {"bevbert_layernorm_res32_fwd": 11, "bevbert_layernorm_res32_bwd": 12, "bevbert_bias_dropout_residual_layernorm_fwd": 9,
+_ROWS_ARG = {"bevbert_layernorm_res32_fwd": 11, "bevbert_layernorm_res32_chain_fwd": 14, "bevbert_layernorm_res32_bwd": 12,
+             "bevbert_bias_dropout_residual_layernorm_fwd": 9,
              "bevbert_layernorm_bwd": 11, "bevbert_layernorm_bwd_add": 12, "bevbert_bias_gelu_fwd": 3, "bevbert_bias_gelu_bwd": 6}
 
 

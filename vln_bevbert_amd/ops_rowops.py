@@ -2,6 +2,7 @@
 LayerNorm (bf16 and fp32 residual streams), dropout, bias + GELU, the SAP / MLM loss tails, embedding sums, the global-map
 segment gather and the BEV lift / splat."""
 import math
+import os
 
 import torch
 
@@ -138,36 +139,67 @@ class _BiasDropResLN(torch.autograd.Function):
                 g1, g2, None)
 
 
+class _Res32Handle:
+    """What rides on ``y16._res32`` when the LayerNorm that made y16 did not write its fp32 output: everything the next
+    LayerNorm of the stream needs to recompute it in its own kernel.  ``z32`` is the producer's second autograd output --
+    the residual gradient of the consumer reaches the producer through it, exactly as it did through y32."""
+    __slots__ = ("z32", "mean", "rstd", "gamma", "beta")
+
+    def __init__(self, z32, mean, rstd, gamma, beta):
+        self.z32, self.mean, self.rstd, self.gamma, self.beta = z32, mean, rstd, gamma, beta
+
+
+def _res32_materialise():
+    """BEVBERT_RES32_Y32=1: every fp32-stream LayerNorm writes its y32, as before the chained form (A/B runs, tests)."""
+    return os.environ.get("BEVBERT_RES32_Y32", "0") == "1"
+
+
 class _BiasDropResLN32(torch.autograd.Function):
     """LayerNorm(dropout(x + bias) + residual) with the fp32 residual stream of ``RT.res32``: x bf16 (a GEMM output),
     residual fp32 (the previous block's ``y32``) or bf16 (where a stream starts); returns (y16, y32).  The backward sums the
     two output gradients in the kernel (bf16 from the GEMMs that read y16, fp32 from the residual add that read y32) and
-    returns dz in fp32 to an fp32 residual."""
+    returns dz in fp32 to an fp32 residual.
+
+    ``prev`` (a _Res32Handle): ``residual`` is the previous LayerNorm's z32 and the kernel recomputes that LayerNorm's fp32
+    output from it (bevbert_layernorm_res32_chain_fwd).  ``lazy``: when a backward will follow (z32 is kept anyway), y32
+    is neither allocated nor written and the outputs are (y16, z32, mean, rstd) -- to be handed on in a _Res32Handle, z32
+    never read as y32.  In both forms the second output's gradient is the gradient of y32 and the third input's the residual's."""
 
     @staticmethod
-    def forward(ctx, x, bias, residual, gamma, beta, eps, drop_p):
+    def forward(ctx, x, bias, residual, gamma, beta, eps, drop_p, prev=None, lazy=False):
         assert x.is_contiguous() and x.dtype == torch.bfloat16 and x.dim() >= 2
         H = x.shape[-1]
         rows = x.numel() // H
         need_grad = any(ctx.needs_input_grad)
+        lazy = lazy and need_grad
         y16 = torch.empty_like(x)
-        y32 = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        y32 = None if lazy else torch.empty(x.shape, dtype=torch.float32, device=x.device)
         z32 = torch.empty(x.shape, dtype=torch.float32, device=x.device) if need_grad else None
         mean = torch.empty(rows, dtype=torch.float32, device=x.device) if need_grad else None
         rstd = torch.empty(rows, dtype=torch.float32, device=x.device) if need_grad else None
         off = RT.next_offset(x.numel()) if drop_p > 0 else 0
         assert residual.is_contiguous() and residual.shape == x.shape and residual.dtype in (torch.float32, torch.bfloat16)
-        call("bevbert_layernorm_res32_fwd", ptr(x), ptr(_f32(bias)) if bias is not None else None, ptr(residual),
-             dtype_code(residual), ptr(_f32(gamma)), ptr(_f32(beta)), ptr(y16), ptr(y32), ptr(z32), ptr(mean), ptr(rstd),
-             rows, H, float(eps), float(drop_p), RT.seed, off, stream())
+        b32 = ptr(_f32(bias)) if bias is not None else None
+        if prev is not None:
+            assert residual.dtype == torch.float32 and prev.mean.numel() == rows and prev.gamma.numel() == H
+            call("bevbert_layernorm_res32_chain_fwd", ptr(x), b32, ptr(residual), ptr(prev.mean), ptr(prev.rstd),
+                 ptr(_f32(prev.gamma)), ptr(_f32(prev.beta)), ptr(_f32(gamma)), ptr(_f32(beta)), ptr(y16), ptr(y32), ptr(z32),
+                 ptr(mean), ptr(rstd), rows, H, float(eps), float(drop_p), RT.seed, off, stream())
+        else:
+            call("bevbert_layernorm_res32_fwd", ptr(x), b32, ptr(residual), dtype_code(residual), ptr(_f32(gamma)),
+                 ptr(_f32(beta)), ptr(y16), ptr(y32), ptr(z32), ptr(mean), ptr(rstd), rows, H, float(eps), float(drop_p),
+                 RT.seed, off, stream())
         ctx.save_for_backward(z32, mean, rstd)
         ctx.params = (bias, gamma, beta)
         ctx.cfg = (rows, H, float(drop_p), RT.seed, off, residual.dtype)
         ctx.set_materialize_grads(False)       # an unused output arrives as None (backward handles it), not as dense zeros
+        if lazy:
+            ctx.mark_non_differentiable(mean, rstd)
+            return y16, z32, mean, rstd        # (the statistics for the handle)
         return y16, y32
 
     @staticmethod
-    def backward(ctx, dy16, dy32):
+    def backward(ctx, dy16, dy32, *_):
         z32, mean, rstd = ctx.saved_tensors
         bias, gamma, beta = ctx.params
         rows, H, drop_p, seed, off, res_dtype = ctx.cfg
@@ -184,7 +216,7 @@ class _BiasDropResLN32(torch.autograd.Function):
                      (dg, db, dbi), ag, rows, H, dev)
         cast = lambda r, p: None if r is None else r.to(p.dtype)
         gres = dz32
-        return dx16, cast(rbi, bias) if bias is not None else None, gres, cast(rg, gamma), cast(rb, beta), None, None
+        return dx16, cast(rbi, bias) if bias is not None else None, gres, cast(rg, gamma), cast(rb, beta), None, None, None, None
 
 
 def bias_dropout_residual_layernorm(x, bias, residual, gamma, beta, eps, drop_p=0.0, training=False,
@@ -192,10 +224,14 @@ def bias_dropout_residual_layernorm(x, bias, residual, gamma, beta, eps, drop_p=
     """LayerNorm(dropout(x + bias) + residual)  -- vilmodel.py:150-154,189-193."""
     p = float(drop_p) if training else 0.0
     if RT.res32 and residual is not None and x.dtype == torch.bfloat16 and x.is_cuda:
-        # fp32 residual stream: the previous block left its fp32 output on the bf16 tensor the model passes around
+        # fp32 residual stream: the previous block left its fp32 output on the bf16 tensor the model passes around -- as a
+        # tensor, or (when a backward follows: its z32 is kept anyway) as the handle to recompute it from
         r32 = getattr(residual, "_res32", None)
-        y16, y32 = _BiasDropResLN32.apply(x, bias, r32 if r32 is not None else residual, gamma, beta, eps, p)
-        y16._res32 = y32
+        prev = r32 if isinstance(r32, _Res32Handle) else None
+        res = prev.z32 if prev is not None else (r32 if r32 is not None else residual)
+        lazy = torch.is_grad_enabled() and not _res32_materialise()
+        y16, *rest = _BiasDropResLN32.apply(x, bias, res, gamma, beta, eps, p, prev, lazy)
+        y16._res32 = rest[0] if len(rest) == 1 else _Res32Handle(*rest, gamma, beta)      # y32 | (z32, mean, rstd)
         return y16
     return _BiasDropResLN.apply(x, bias, residual, gamma, beta, eps, p, inplace_z, None, None)
 
