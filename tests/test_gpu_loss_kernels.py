@@ -34,10 +34,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.kernel_gates import U8, U24, Worst            # (Worst's default prefix: "loss-kernel-errors:")
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 NEG = -float("inf")
-U24, U8 = 2.0 ** -24, 2.0 ** -8
 DTYPES = [torch.float32, torch.bfloat16]
 _ID = {torch.float32: "f32", torch.bfloat16: "bf16"}.get
 
@@ -49,36 +50,6 @@ def ops():
     from vln_bevbert_amd import lib, ops as _ops
     lib.load()          # raises (does not skip) when the HIP library is missing on a GPU box
     return _ops
-
-
-class Worst:
-    """Worst error of the kernel per quantity over the inner cases of one test, with torch-fp32's error and the gate of
-    that same inner case; report() prints one line per quantity."""
-
-    def __init__(self, tag):
-        self.tag, self.rows = tag, {}
-
-    def check(self, what, got, want, ref32, floor, bf16_out=False, relative=False, where=""):
-        """got: the kernel's result; want: fp64; ref32: torch's fp32 composition; floor: the kernel's earlier gate as a
-        multiple of max(1, |want|max) (relative: of |want|max)."""
-        got, want, ref32 = got.detach().double().cpu(), want.detach().double().cpu(), ref32.detach().double().cpu()
-        assert got.shape == want.shape == ref32.shape, (what, got.shape, want.shape, ref32.shape)
-        top = float(want.abs().max()) if want.numel() else 0.0
-        e32 = float((ref32 - want).abs().max()) if want.numel() else 0.0
-        gate = max(floor * (top if relative else max(1.0, top)), 4.0 * e32)
-        err = (got - want).abs()
-        allow = gate + (U8 * want.abs() if bf16_out else 0.0)
-        worst = float(err.max()) if want.numel() else 0.0
-        row = self.rows.get(what)
-        if row is None or worst > row[0]:
-            self.rows[what] = (worst, e32, gate, where)
-        assert bool((err <= allow).all()), (self.tag, what, where, "kernel", worst, "torch-fp32", e32, "gate", gate,
-                                            "+ 2^-8 |want|" if bf16_out else "")
-
-    def report(self):
-        for what, (worst, e32, gate, where) in self.rows.items():
-            print(f"loss-kernel-errors: {self.tag:<44} {what:<12} kernel {worst:.3e}  torch-fp32 {e32:.3e}  gate {gate:.3e}"
-                  f"{'  at ' + where if where else ''}")
 
 
 # ----------------------------------------------------------------------------- SAP: reference and inputs
