@@ -1,7 +1,8 @@
 """The row kernels every encoder layer runs, on the MI355X against plain fp64 references at their shape and value edges:
 bevbert_bias_gelu/relu_fwd/bwd with the column sums behind them, bevbert_rows_gather / bevbert_rows_scatter and ops.take_rows,
 bevbert_segment_wsum with SegmentCSR, bevbert_embed_sum_layernorm_fwd with _EmbedLN.backward (plain tensors and the arena
-route), bevbert_graph_bias_fwd/bwd, bevbert_dropout_add and bevbert_cast_f32 (csrc/rowops.hip, ops_rowops.py).
+route), bevbert_graph_bias_fwd/bwd, bevbert_dropout_add and bevbert_cast_f32 (csrc/colwise.hip, gather.hip, layernorm.hip, pointwise.hip, optimizer.hip;
+ops_rowops.py).
 
 Inputs and references live in tests/body_cases.py, written in fp64 on the values the kernel gets (bf16 inputs are rounded
 to bf16 first, then widened); tests/test_body_refs_host.py pins them to the plain torch compositions on the CPU.  Branches

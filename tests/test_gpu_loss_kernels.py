@@ -1,6 +1,6 @@
 """The loss-head kernels on the MI355X against plain fp64 torch, at the edges of their shapes and magnitudes:
-bevbert_sap_loss_fwd/bwd, bevbert_cross_entropy_fwd/bwd (csrc/sap_loss.hip), bevbert_bce_rows_fwd/bwd, bevbert_sem_select,
-bevbert_weighted_mean_fwd/bwd and bevbert_colsum_any (csrc/rowops.hip).
+bevbert_sap_loss_fwd/bwd, bevbert_cross_entropy_fwd/bwd, bevbert_bce_rows_fwd/bwd, bevbert_sem_select,
+bevbert_weighted_mean_fwd/bwd (csrc/sap_loss.hip) and bevbert_colsum_any (csrc/colwise.hip).
 
 Every reference is written here in fp64 on the values the kernel gets (bf16 inputs are rounded to bf16 first, then
 widened).  The SAP reference (sap_logits_ref / sap_ref) restates forward_sap's tail without pretrain_cmt.fuse_sap_logits;

@@ -1,5 +1,5 @@
 """ParamArena.clip_and_step on the MI355X against the float64 reference of tests/optimizer_ref.py: sumsq_kernel,
-clip_coef_kernel and adamw_kernel (csrc/rowops.hip) with the moments compared, not only the parameters.
+clip_coef_kernel and adamw_kernel (csrc/optimizer.hip) with the moments compared, not only the parameters.
 
 The probe arena (optimizer_ref.PROBE, 2.12 M elements) has tensors on both sides of the 1024-element chunk edge, two
 packed groups, the three no-decay name patterns, a tensor first touched at step 3, one touched once and then stepped on

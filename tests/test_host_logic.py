@@ -244,10 +244,8 @@ def _dtype_answer_rows(l):
     strides = (ctypes.c_int64 * 8)(*([64] * 8))
     unsup, inval = -3, -1
     return [
-        # rowops.hip
+        # colwise.hip
         ("colsum_any", lambda dt: l.bevbert_colsum_any(N, N, 1, 4, dt, 0, N), unsup, "colsum_any: dtype %d unsupported"),
-        ("bce_rows_fwd", lambda dt: l.bevbert_bce_rows_fwd(N, N, N, N, 1, 4, dt, N), unsup, "bce_rows_fwd: dtype %d unsupported"),
-        ("bce_rows_bwd", lambda dt: l.bevbert_bce_rows_bwd(N, N, N, N, N, 1, 4, dt, N), unsup, "bce_rows_bwd: dtype %d unsupported"),
         ("bias_gelu_fwd", lambda dt: l.bevbert_bias_gelu_fwd(N, N, N, 1, 4, dt, N), unsup, "bias_act_fwd: dtype %d unsupported"),
         ("bias_gelu_fwd C=8", lambda dt: l.bevbert_bias_gelu_fwd(N, N, N, 1, 8, dt, N), unsup, "bias_act_fwd: dtype %d unsupported"),
         ("bias_relu_fwd", lambda dt: l.bevbert_bias_relu_fwd(N, N, N, 1, 4, dt, N), unsup, "bias_act_fwd: dtype %d unsupported"),
@@ -255,14 +253,16 @@ def _dtype_answer_rows(l):
         ("bias_relu_bwd", lambda dt: l.bevbert_bias_relu_bwd(N, N, N, N, N, N, 1, 4, dt, 0, N), unsup, "bias_act_bwd: dtype %d unsupported"),
         ("colsum", lambda dt: l.bevbert_colsum(N, N, N, 1, 4, dt, 0, N), unsup, "colsum: dtype %d unsupported"),
         ("colsum_partials", lambda dt: l.bevbert_colsum_partials(N, N, 1, 4, dt, N), unsup, "colsum_partials: dtype %d unsupported"),
+        # gather.hip
         ("segment_wsum", lambda dt: l.bevbert_segment_wsum(N, N, N, N, N, 1, 4, dt, N), unsup, "segment_wsum: dtype %d unsupported"),
-        ("accum_partials", lambda dt: l.bevbert_accum_partials(N, N, 1, 4, dt, N), unsup, "accum_partials: dtype %d unsupported"),
         ("rows_gather", lambda dt: l.bevbert_rows_gather(N, N, N, 1, 4, dt, N), unsup, "rows_gather: dtype %d unsupported"),
         ("rows_scatter", lambda dt: l.bevbert_rows_scatter(N, N, N, 1, 4, dt, 0, N), unsup, "rows_scatter: dtype %d unsupported"),
         ("rows_scatter +=", lambda dt: l.bevbert_rows_scatter(N, N, N, 1, 4, dt, 1, N), unsup, "rows_scatter: dtype %d unsupported"),
         ("embedding_grad", lambda dt: l.bevbert_embedding_grad(N, N, N, 1, 4, 0, dt, N), unsup, "embedding_grad: dtype %d unsupported"),
         ("embedding_grad_sliced", lambda dt: l.bevbert_embedding_grad_sliced(N, N, N, 1, 4, 1, 1, dt, N), unsup,
          "embedding_grad_sliced: dtype %d unsupported"),
+        # optimizer.hip
+        ("accum_partials", lambda dt: l.bevbert_accum_partials(N, N, 1, 4, dt, N), unsup, "accum_partials: dtype %d unsupported"),
         ("cast_f32", lambda dt: l.bevbert_cast_f32(N, N, 4, dt, N), unsup, "cast_f32: dst dtype %d unsupported"),
         # smallk.hip
         ("smallk_fwd", lambda dt: l.bevbert_smallk_linear_layernorm_fwd(*[N] * 11, 1, 1, 256, 1e-12, dt, N), unsup,
@@ -274,6 +274,8 @@ def _dtype_answer_rows(l):
         ("sap_loss_bwd", lambda dt: l.bevbert_sap_loss_bwd(*[N] * 7, 1, 1, 1, dt, N), unsup, "sap_loss: dtype %d unsupported"),
         ("cross_entropy_fwd", lambda dt: l.bevbert_cross_entropy_fwd(N, N, N, N, 1, 4, dt, N), unsup, "cross_entropy: dtype %d unsupported"),
         ("cross_entropy_bwd", lambda dt: l.bevbert_cross_entropy_bwd(N, N, N, N, N, 1, 4, dt, N), unsup, "cross_entropy: dtype %d unsupported"),
+        ("bce_rows_fwd", lambda dt: l.bevbert_bce_rows_fwd(N, N, N, N, 1, 4, dt, N), unsup, "bce_rows_fwd: dtype %d unsupported"),
+        ("bce_rows_bwd", lambda dt: l.bevbert_bce_rows_bwd(N, N, N, N, N, 1, 4, dt, N), unsup, "bce_rows_bwd: dtype %d unsupported"),
         # nav_expert.hip
         ("nav_ce_fwd", lambda dt: l.bevbert_nav_ce_fwd(N, N, N, 1, 4, -100, dt, N), unsup, "nav_ce: dtype %d unsupported"),
         ("nav_ce_bwd", lambda dt: l.bevbert_nav_ce_bwd(N, N, N, N, N, 1, 4, -100, dt, N), unsup, "nav_ce: dtype %d unsupported"),

@@ -37,7 +37,7 @@ BEVBERT_API int bevbert_zero(void* p, int64_t bytes, hipStream_t stream) {
   return BB_OK;
 }
 
-BEVBERT_API int bevbert_version(void) { return 300; }  // 0.3.0: bevbert_layernorm_res32_chain_fwd (csrc/rowops.hip)
+BEVBERT_API int bevbert_version(void) { return 300; }  // 0.3.0: bevbert_layernorm_res32_chain_fwd (csrc/layernorm.hip)
 
 static const uint32_t* g_step_salt = nullptr;
 const uint32_t* bb_step_salt() { return g_step_salt; }
@@ -345,12 +345,6 @@ BEVBERT_API const char* bevbert_attn_plan(int B, int nh, int Lq, int Lk, int dty
   return ATTN_KERNEL_NAMES[backward ? attn_plan_bwd(a, dtype, impl, kn) : attn_plan_fwd(a, dtype, impl, bits_ready != 0, kn).kernel];
 }
 
-// Test hook: materialise the dropout keep-mask the kernels derive from (seed, offset + element index).
-__global__ void keep_mask_kernel(uint8_t* out, size_t n, uint32_t key, uint32_t thr, const uint32_t* salt) {
-  key = bb_salted(key, salt);
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
-    out[i] = (uint8_t)bb_keep(key, (uint32_t)i, thr);
-}
 // Size of the keep-bit matrix of an attention call (64-bit words), see attn_common.h.
 BEVBERT_API int64_t bevbert_attn_drop_bits_words(int B, int nh, int Lq, int Lk) {
   return 3 * bits_words_one(B, nh, Lq, Lk);
@@ -367,15 +361,4 @@ BEVBERT_API int bevbert_attn_drop_bits(uint64_t* drop_bits, int B, int nh, int L
   if (rc != BB_OK) return rc;
   const int64_t one = bits_words_one(B, nh, Lq, Lk);
   return attn_drop_bits(a, drop_bits, drop_bits + one, reinterpret_cast<uint32_t*>(drop_bits + 2 * one), stream);
-}
-
-BEVBERT_API int bevbert_dropout_keep_mask(uint8_t* out, int64_t n, float drop_p, uint64_t seed, uint64_t offset,
-                                          hipStream_t stream) {
-  if (n <= 0) return BB_OK;
-  size_t nb = ((size_t)n + 255) / 256;
-  if (nb > 4096) nb = 4096;
-  hipLaunchKernelGGL(keep_mask_kernel, dim3(nb), dim3(256), 0, stream, out, (size_t)n, bb_site_key(seed, offset),
-                     bb_drop_threshold(drop_p), bb_step_salt());
-  BB_CHECK_LAUNCH("dropout_keep_mask");
-  return BB_OK;
 }

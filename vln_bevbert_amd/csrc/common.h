@@ -149,7 +149,7 @@ __device__ __forceinline__ float wave_max(float v) {
 // ---- LayerNorm of a row held in registers ---------------------------------------------------
 // One wave owns a row of H = NV * 256 values, NV float4s per lane.  A kernel of the LayerNorm family takes its statistics
 // and its affine step from here, so that kernels that see the same row give the same bits.  ln_fwd_kernel,
-// ln_res32_fwd_kernel (rowops.hip) and smallk_ln_fwd_kernel (smallk.hip) still carry the text of ln_row_stats themselves:
+// ln_res32_fwd_kernel (layernorm.hip) and smallk_ln_fwd_kernel (smallk.hip) still carry the text of ln_row_stats themselves:
 // called from here their rstd changes in the last bit (see ln_fwd_kernel).
 __device__ __forceinline__ void add4(float4& a, const float4 b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; }
 // two-pass variance, eps inside the square root

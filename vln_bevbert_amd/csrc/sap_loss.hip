@@ -12,6 +12,10 @@
 // In PyTorch this is ~35 elementwise / reduction launches forward and as many backward, each on a (B, <= 64) tensor.
 // One wave per sample does all of it: lane j owns global-map node j and BEV candidate j.  The kernel also leaves the
 // gradients w.r.t. the three head outputs for a unit upstream gradient; sap_loss_grad scales them by dloss[b].
+//
+// Below it, the other loss-head kernels, each under its own section comment: the row-wise cross-entropy of the MLM head,
+// the weighted mean of the step's loss (pretrain_src/train_r2r.py:263), and the semantic head's row selection and
+// binary cross-entropy (pretrain_cmt.py:391-441).
 #include "common.h"
 
 template <typename T>
@@ -224,5 +228,148 @@ BEVBERT_API int bevbert_cross_entropy_bwd(const void* logits, const int64_t* tar
   });
   if (!type_ok) return bb_dtype_unsupported("cross_entropy", dtype);
   BB_CHECK_LAUNCH("cross_entropy_bwd");
+  return BB_OK;
+}
+
+// loss.mean() of the step (pretrain_src/train_r2r.py:263) with the zero-weight padding rows of a static batch:
+// out = sum_i w[i] * x[i] / denom   (w NULL: all ones; denom from device memory when denom_dev is given -- the number of
+// real rows of the batch that currently sits in the buffers).  One workgroup (n is at most a few thousand), fixed order.
+__global__ __launch_bounds__(1024) void weighted_mean_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                                 const float* __restrict__ denom_dev, float denom, int n,
+                                                                 float* __restrict__ out) {
+  __shared__ float sh[16];
+  float s = 0.f;
+  for (int i = threadIdx.x; i < n; i += 1024) s += (w ? w[i] : 1.0f) * x[i];
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t = 0.f;
+    for (int i = 0; i < 16; ++i) t += sh[i];
+    *out = t / (denom_dev ? *denom_dev : denom);
+  }
+}
+__global__ __launch_bounds__(256) void weighted_mean_bwd_kernel(const float* __restrict__ dout, const float* __restrict__ w,
+                                                                const float* __restrict__ denom_dev, float denom, int n,
+                                                                float* __restrict__ dx) {
+  const float g = *dout / (denom_dev ? *denom_dev : denom);
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) dx[i] = (w ? w[i] : 1.0f) * g;
+}
+
+BEVBERT_API int bevbert_weighted_mean_fwd(const float* x, const float* w, const float* denom_dev, float denom, int n,
+                                          float* out, hipStream_t stream) {
+  BB_REQUIRE(n > 0 && x != nullptr && out != nullptr, "weighted_mean_fwd: empty input");
+  hipLaunchKernelGGL(weighted_mean_fwd_kernel, dim3(1), dim3(1024), 0, stream, x, w, denom_dev, denom, n, out);
+  BB_CHECK_LAUNCH("weighted_mean_fwd");
+  return BB_OK;
+}
+
+BEVBERT_API int bevbert_weighted_mean_bwd(const float* dout, const float* w, const float* denom_dev, float denom, int n,
+                                          float* dx, hipStream_t stream) {
+  BB_REQUIRE(n > 0 && dout != nullptr && dx != nullptr, "weighted_mean_bwd: empty input");
+  int nb = (n + 255) / 256;
+  if (nb > 256) nb = 256;
+  hipLaunchKernelGGL(weighted_mean_bwd_kernel, dim3(nb), dim3(256), 0, stream, dout, w, denom_dev, denom, n, dx);
+  BB_CHECK_LAUNCH("weighted_mean_bwd");
+  return BB_OK;
+}
+
+// Semantic head (pretrain_cmt.py:391-441, MaskSEM / SEM): the supervised cells are those of a boolean mask (two masks ANDed
+// for MaskSEM) -- a data-dependent count only the device knows.  sem_select: ONE workgroup compacts their row numbers into a
+// fixed-capacity index (padding: row 0, weight 0), and leaves the weights and the divisor of the mean (count x classes).
+// bce_rows: sum over the classes of binary_cross_entropy_with_logits for the selected rows, labels read through the index.
+__global__ __launch_bounds__(1024) void sem_select_kernel(const uint8_t* __restrict__ m1, const uint8_t* __restrict__ m2, int n,
+                                                         int cap, int classes, int64_t* __restrict__ idx,
+                                                         float* __restrict__ valid, float* __restrict__ denom) {
+  __shared__ int s_cnt[1024];
+  const int t = threadIdx.x;
+  const int per = (n + 1023) / 1024, lo = t * per, hi = min(n, lo + per);
+  int c = 0;
+  for (int i = lo; i < hi; ++i) c += (m1[i] != 0) && (m2 == nullptr || m2[i] != 0);
+  s_cnt[t] = c;
+  __syncthreads();
+  for (int off = 1; off < 1024; off <<= 1) {       // inclusive scan (Hillis-Steele; 10 rounds on 1024 counters)
+    const int v = (t >= off) ? s_cnt[t - off] : 0;
+    __syncthreads();
+    s_cnt[t] += v;
+    __syncthreads();
+  }
+  const int total = s_cnt[1023];
+  int pos = s_cnt[t] - c;
+  for (int i = lo; i < hi; ++i)
+    if ((m1[i] != 0) && (m2 == nullptr || m2[i] != 0)) {
+      if (pos < cap) idx[pos] = i;
+      ++pos;
+    }
+  const int kept = total < cap ? total : cap;
+  for (int i = t; i < cap; i += 1024) {
+    if (i >= kept) idx[i] = 0;
+    valid[i] = i < kept ? 1.0f : 0.0f;
+  }
+  if (t == 0) *denom = (float)total * (float)classes;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void bce_rows_fwd_kernel(const T* __restrict__ x, const uint8_t* __restrict__ labels,
+                                                           const int64_t* __restrict__ idx, float* __restrict__ out, int rows,
+                                                           int C) {
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const uint8_t* lab = labels + (size_t)(idx ? idx[row] : row) * C;
+  float s = 0.f;
+  for (int c = lane; c < C; c += 64) {
+    const float v = io<T>::ld(x + (size_t)row * C + c), y = lab[c] ? 1.0f : 0.0f;
+    s += fmaxf(v, 0.f) - v * y + log1pf(__expf(-fabsf(v)));       // the numerically stable form torch uses
+  }
+  s = wave_sum(s);
+  if (lane == 0) out[row] = s;
+}
+template <typename T>
+__global__ __launch_bounds__(256) void bce_rows_bwd_kernel(const T* __restrict__ x, const uint8_t* __restrict__ labels,
+                                                           const int64_t* __restrict__ idx, const float* __restrict__ g,
+                                                           T* __restrict__ dx, int rows, int C) {
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const uint8_t* lab = labels + (size_t)(idx ? idx[row] : row) * C;
+  const float gr = g[row];
+  for (int c = lane; c < C; c += 64) {
+    const float v = io<T>::ld(x + (size_t)row * C + c), y = lab[c] ? 1.0f : 0.0f;
+    io<T>::st(dx + (size_t)row * C + c, (1.0f / (1.0f + __expf(-v)) - y) * gr);
+  }
+}
+
+BEVBERT_API int bevbert_sem_select(const uint8_t* mask1, const uint8_t* mask2, int n, int cap, int classes, int64_t* idx,
+                                   float* valid, float* denom, hipStream_t stream) {
+  BB_REQUIRE(mask1 != nullptr && n > 0 && cap > 0 && classes > 0, "sem_select: bad arguments");
+  hipLaunchKernelGGL(sem_select_kernel, dim3(1), dim3(1024), 0, stream, mask1, mask2, n, cap, classes, idx, valid, denom);
+  BB_CHECK_LAUNCH("sem_select");
+  return BB_OK;
+}
+
+BEVBERT_API int bevbert_bce_rows_fwd(const void* logits, const uint8_t* labels, const int64_t* idx, float* out, int rows,
+                                     int C, int dtype, hipStream_t stream) {
+  BB_REQUIRE(rows >= 0 && C > 0, "bce_rows_fwd: rows=%d C=%d", rows, C);
+  if (rows == 0) return BB_OK;
+  const dim3 grid((rows + 3) / 4);
+  const bool type_ok = bb_with_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(bce_rows_fwd_kernel<T>, grid, dim3(256), 0, stream, (const T*)logits, labels, idx, out, rows, C);
+  });
+  if (!type_ok) return bb_dtype_unsupported("bce_rows_fwd", dtype);
+  BB_CHECK_LAUNCH("bce_rows_fwd");
+  return BB_OK;
+}
+
+BEVBERT_API int bevbert_bce_rows_bwd(const void* logits, const uint8_t* labels, const int64_t* idx, const float* g, void* dlogits,
+                                     int rows, int C, int dtype, hipStream_t stream) {
+  BB_REQUIRE(rows >= 0 && C > 0, "bce_rows_bwd: rows=%d C=%d", rows, C);
+  if (rows == 0) return BB_OK;
+  const dim3 grid((rows + 3) / 4);
+  const bool type_ok = bb_with_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(bce_rows_bwd_kernel<T>, grid, dim3(256), 0, stream, (const T*)logits, labels, idx, g, (T*)dlogits, rows, C);
+  });
+  if (!type_ok) return bb_dtype_unsupported("bce_rows_bwd", dtype);
+  BB_CHECK_LAUNCH("bce_rows_bwd");
   return BB_OK;
 }

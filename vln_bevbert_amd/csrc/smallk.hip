@@ -13,7 +13,7 @@
 // kernels than to move -- the forward writes only y, the backward reads only dy (no z, no dz tensor):
 //
 //   forward   W^T staged once per workgroup in LDS ([K][H] fp32); a wave owns a row, its features are broadcast from
-//             lanes 0..K-1; statistics, affine, post terms and the gathered table row as in ln_fwd_kernel (rowops.hip);
+//             lanes 0..K-1; statistics, affine, post terms and the gathered table row as in ln_fwd_kernel (layernorm.hip);
 //   backward  phase A (wave per row): z recomputed, LayerNorm backward -> dz (fp32) into an LDS tile of R rows, running
 //             column sums of dy * xhat (dgamma), dy (dbeta), dz (dbias) in registers;
 //             phase B (thread per column triple): dW[c][k] += dz[r][c] * feat[r][k] over the R rows of the tile;

@@ -7,7 +7,7 @@
 //   ResidualAttentionBlock.forward, QuickGELU      encoders/clip/model.py:162-188
 //   grid_pool_depth = AdaptiveAvgPool2d((14, 14))  models/Policy_ViewSelection_BEV.py:127,190
 //
-// Layout as in rowops.hip: activations are (rows, H) row-major with H % 256 == 0 and H <= 1024; one 64-lane wave owns one
+// Layout as in layernorm.hip: activations are (rows, H) row-major with H % 256 == 0 and H <= 1024; one 64-lane wave owns one
 // row and keeps it in registers (H / 64 values per lane as float4s).  The residual stream z32 is fp32 whatever the compute
 // dtype T of the GEMM operands; statistics are fp32, and every LayerNorm here is ln_row_stats + ln_norm4 (common.h), the
 // row body of ln_fwd_kernel.  No atomics, plain vector stores, one launch per entry.

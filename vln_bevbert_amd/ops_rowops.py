@@ -81,7 +81,7 @@ class _BiasDropResLN(torch.autograd.Function):
         if residual is not None:
             assert residual.is_contiguous() and residual.shape == x.shape and residual.dtype == x.dtype
         if post1 is not None or post2 is not None:
-            # y = LN(x + bias) + post1 + post2: the sums that follow the LayerNorm ride on its store (rowops.hip)
+            # y = LN(x + bias) + post1 + post2: the sums that follow the LayerNorm ride on its store (layernorm.hip)
             assert residual is None and drop_p == 0, "post terms: plain bias + LayerNorm only"
             for t in (post1, post2):
                 assert t is None or (t.is_contiguous() and t.shape == x.shape and t.dtype == x.dtype)
