@@ -76,11 +76,14 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(AttnArgs a, float* __re
   if (lane == 0) delta[((size_t)b * a.nh + h) * a.Lq + qi] = s;
 }
 
-// dQ (and dbias): one wave per query row
-template <typename T>
+// dQ (and dbias): one wave per query row.  OWN_DELTA (bf16 storage): delta is not taken from sum_d dO O of the stored O,
+// whose bf16 rounding reaches dS at 2^-9 sum_d |O||dO| per row, but summed here as sum_k Pd dPd in fp32 and published in
+// a.delta for the dK/dV kernel that follows on the stream.
+template <typename T, bool OWN_DELTA>
 __global__ __launch_bounds__(256) void attn_simple_dq_kernel(AttnArgs a) {
   if (a.drop_p > 0.f) a.drop_key = bb_salted(a.drop_key, a.salt);
   __shared__ float s_ds[4][LK_MAX];
+  __shared__ float s_dp[OWN_DELTA ? 4 : 1][OWN_DELTA ? LK_MAX : 1];
   __shared__ float s_q[4][ATTN_D];
   __shared__ float s_do[4][ATTN_D];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -94,16 +97,32 @@ __global__ __launch_bounds__(256) void attn_simple_dq_kernel(AttnArgs a) {
   s_do[w][lane] = io<T>::ld(dorow + lane);
   __builtin_amdgcn_wave_barrier();
   const size_t ridx = ((size_t)b * a.nh + h) * a.Lq + qi;
-  const float lse = a.lse[ridx], delta = a.delta[ridx];
+  const float lse = a.lse[ridx];
+  float delta = OWN_DELTA ? 0.f : a.delta[ridx];
   const float keep_scale = a.drop_p > 0.f ? 1.0f / (1.0f - a.drop_p) : 1.0f;
   for (int key = lane; key < a.Lk; key += 64) {
     const float s = score<T>(a, kbase, s_q[w], b, qi, key);
     const float p = __expf(s - lse);
     float dp = dot64_row<T>(vbase + (size_t)key * a.ldv, s_do[w]);
     if (a.drop_p > 0.f) dp = bb_keep(a.drop_key, attn_elem(a, b, h, qi, key), a.drop_thr) ? dp * keep_scale : 0.f;
+    if constexpr (OWN_DELTA) {
+      s_ds[w][key] = p;
+      s_dp[w][key] = dp;
+      delta += p * dp;
+      continue;
+    }
     const float ds = p * (dp - delta);
     s_ds[w][key] = ds;
     if (a.dbias) a.dbias[(((size_t)b * a.nh + h) * a.Lq + qi) * a.Lk + key] = ds;
+  }
+  if constexpr (OWN_DELTA) {
+    delta = wave_sum(delta);
+    if (lane == 0) const_cast<float*>(a.delta)[ridx] = delta;   // consumed by the dK/dV kernel
+    for (int key = lane; key < a.Lk; key += 64) {        // each lane revisits the keys it wrote itself
+      const float ds = s_ds[w][key] * (s_dp[w][key] - delta);
+      s_ds[w][key] = ds;
+      if (a.dbias) a.dbias[(((size_t)b * a.nh + h) * a.Lq + qi) * a.Lk + key] = ds;
+    }
   }
   __builtin_amdgcn_wave_barrier();
   float acc = 0.f;
@@ -161,11 +180,12 @@ int attn_delta(const AttnArgs& a, float* delta, int dtype, hipStream_t st) {
   return BB_OK;
 }
 
+// a.delta: filled by attn_delta beforehand for fp32 tensors; bf16 storage: written by the dQ kernel (OWN_DELTA)
 int attn_simple_bwd(const AttnArgs& a, int dtype, hipStream_t st) {
   BB_REQUIRE(a.Lk <= LK_MAX, "attention (exact path): Lk=%d exceeds %d", a.Lk, LK_MAX);
   const dim3 gq((a.Lq + 3) / 4, a.nh, a.B), gk((a.Lk + 3) / 4, a.nh, a.B);
   bb_with_type(dtype, [&](auto t) {
-    hipLaunchKernelGGL(attn_simple_dq_kernel<decltype(t)>, gq, dim3(256), 0, st, a);
+    hipLaunchKernelGGL((attn_simple_dq_kernel<decltype(t), sizeof(t) == 2>), gq, dim3(256), 0, st, a);
     hipLaunchKernelGGL(attn_simple_dkv_kernel<decltype(t)>, gk, dim3(256), 0, st, a);
   });
   BB_CHECK_LAUNCH("attn_bwd(exact)");

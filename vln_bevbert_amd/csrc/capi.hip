@@ -299,8 +299,10 @@ BEVBERT_API int bevbert_attn_bwd(const void* q, const void* k, const void* v, co
   a.o = const_cast<void*>(o); a.dout = dout; a.lse = const_cast<float*>(lse); a.delta = delta_ws;
   a.dq = dq; a.dk = dk; a.dv = dv; a.dbias = dbias;
   const AttnKernel kernel = attn_plan_bwd(a, dtype, impl, attn_read_knobs(0));
-  // the MFMA kernels compute delta themselves (the dQ kernel publishes it for the dK/dV kernel)
-  if ((kernel == AK_attn_f32_bwd || kernel == AK_attn_simple_bwd) && (rc = attn_delta(a, delta_ws, dtype, stream)) != BB_OK)
+  // the MFMA kernels compute delta themselves (the dQ kernel publishes it for the dK/dV kernel), and so does the exact
+  // kernel on bf16 storage, where sum_d dO O would carry the rounding of the stored O (attn_simple.hip)
+  if ((kernel == AK_attn_f32_bwd || (kernel == AK_attn_simple_bwd && dtype == BB_F32)) &&
+      (rc = attn_delta(a, delta_ws, dtype, stream)) != BB_OK)
     return rc;
   g_attn_path[1] = ATTN_KERNEL_NAMES[kernel];
   switch (kernel) {
