@@ -417,6 +417,20 @@ int bevbert_cross_entropy_fwd(const void* logits, const int64_t* target, float* 
 int bevbert_cross_entropy_bwd(const void* logits, const int64_t* target, const float* lse, const float* dloss,
                               void* dlogits, int rows, int C, int dtype, hipStream_t stream);
 
+/* F.kl_div(F.log_softmax(logits.float(), -1), t, reduction="none").sum(1) for finite logits and t >= 0 -- the MRC head
+ * (pretrain_cmt.py:272-297, rows = masked objects, C = detector classes).  logits (rows, C) bf16 / fp32, contiguous, base
+ * 16-byte aligned, any C >= 1; targets (N, C) f32; idx (rows) i64 or NULL: row r reads targets[idx[r]] (NULL: row r;
+ * duplicates allowed).  loss[r] = sum_c xlogy(t, t) - t * ((x - m) - ls) in fp32, a term with t == 0 adds exactly 0.
+ * stats (3 x rows floats) = the row maxima m, then ls = log sum_c exp(x - m) (apart, as in cross_entropy_fwd), then
+ * S = sum_c t.  bwd: stats as the forward left them; dlogits = (exp((x - m) - ls) * S[r] - t) * dloss[r] in the logits'
+ * dtype (dlogits may alias logits) -- the factor S because detector probabilities do not sum to 1 exactly.  targets get no
+ * gradient.  C <= 1024: one wave per row, else one workgroup per row; no atomics.  rows <= 0 returns 0; a NULL logits /
+ * targets / output pointer with rows > 0 is an argument error (idx alone may be NULL). */
+int bevbert_soft_ce_fwd(const void* logits, const float* targets, const int64_t* idx, float* loss, float* stats, int rows,
+                        int C, int dtype, hipStream_t stream);
+int bevbert_soft_ce_bwd(const void* logits, const float* targets, const int64_t* idx, const float* stats, const float* dloss,
+                        void* dlogits, int rows, int C, int dtype, hipStream_t stream);
+
 /* Per-step dropout salt.  Every dropout site derives its mask from hash(seed, offset) -- launch arguments, frozen in a
  * captured hipGraph.  After bevbert_set_step_salt(word) (word: 4 bytes of device memory owned by the caller, NULL to
  * clear) every dropout kernel of the library uses hash(site_key ^ *word): the host rewrites the word once per training
@@ -737,6 +751,15 @@ int bevbert_ce_sample_action(const void* logits, int dtype, int B, int C, const 
  * loads where a row starts on a 16-byte boundary.  NaN logits are not ranked as torch.argmax ranks them. */
 int bevbert_val_ce_rows(const void* logits, int64_t ld, const int64_t* target, const float* valid, int R, int C, int dtype,
                         void* acc, void* scratch, hipStream_t stream);
+
+/* val_kl_rows (MRC, train_reverie_obj.py:415-446): logits as in val_ce_rows; targets (N, C) f32 contiguous, row r reads
+ * targets[idx[r]] (idx (R) i64 or NULL: row r); valid (R) f32 or NULL.  sum += the row's KL as bevbert_soft_ce_fwd defines
+ * it (fp32 statistics m and s; the terms formed and summed per row in fp64, the row's sum rounded to fp32 once for its
+ * record, the records added in fp64), a += (arg-max of the logits == arg-max of the target row, the lowest index on
+ * a tie on both sides), b += 1.  A row with valid == 0 adds nothing.  Same record layout, fold and scratch (8 bytes per
+ * row) as val_ce_rows. */
+int bevbert_val_kl_rows(const void* logits, int64_t ld, const float* targets, const int64_t* idx, const float* valid, int R,
+                        int C, int dtype, void* acc, void* scratch, hipStream_t stream);
 
 /* val_bce_keys: logits (R, C) f32 / bf16 (row stride ld), labels uint8 rows read through idx (i64, NULL: row r) as in
  * bce_rows_fwd, valid (R) f32 or NULL.  sum += BCE-with-logits over the valid rows' elements, a += valid rows.  Element

@@ -14,8 +14,8 @@
 // gradients w.r.t. the three head outputs for a unit upstream gradient; sap_loss_grad scales them by dloss[b].
 //
 // Below it, the other loss-head kernels, each under its own section comment: the row-wise cross-entropy of the MLM head,
-// the weighted mean of the step's loss (pretrain_src/train_r2r.py:263), and the semantic head's row selection and
-// binary cross-entropy (pretrain_cmt.py:391-441).
+// the weighted mean of the step's loss (pretrain_src/train_r2r.py:263), the semantic head's row selection and
+// binary cross-entropy (pretrain_cmt.py:391-441), and the soft-target cross-entropy of the MRC head (pretrain_cmt.py:272-297).
 #include "common.h"
 
 template <typename T>
@@ -371,5 +371,149 @@ BEVBERT_API int bevbert_bce_rows_bwd(const void* logits, const uint8_t* labels, 
   });
   if (!type_ok) return bb_dtype_unsupported("bce_rows_bwd", dtype);
   BB_CHECK_LAUNCH("bce_rows_bwd");
+  return BB_OK;
+}
+
+// =============================================================================================
+// Soft-target cross-entropy rows (the MRC head, pretrain_cmt.py:272-297: F.kl_div(F.log_softmax(pred.float()), probs,
+// reduction="none").sum(1) over rows = masked objects, C = detector classes).  Logits in their own dtype, target rows
+// fp32 read through an optional row index (duplicates allowed), statistics in fp32:
+//   loss[r] = sum_c xlogy(t, t) - t * ((x - m) - ls)       m = row maximum, ls = log sum exp(x - m); t == 0 adds exactly 0
+//   stats   = m (rows) | ls (rows) | S = sum_c t (rows)    m and ls apart for the reason given at ce_bwd_kernel
+//   dlogits = (exp((x - m) - ls) * S - t) * dloss[r]       the detector's probabilities do not sum to 1 exactly
+// About 100 rows of 1000 columns per step: one wave per row up to SOFT_CE_WAVE_ROW_MAX columns (four rows per workgroup),
+// one workgroup per row beyond.  Rows need not start aligned: the ce_span split above.
+// =============================================================================================
+#define SOFT_CE_WAVE_ROW_MAX 1024
+
+// sum / maximum over the NT threads that share a row (NT = 64: the wave; 256: the workgroup, through sh[4])
+template <int NT> __device__ __forceinline__ float row_sum(float v, float* sh) {
+  v = wave_sum(v);
+  if constexpr (NT == 64) {
+    return v;
+  } else {
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+  }
+}
+template <int NT> __device__ __forceinline__ float row_max(float v, float* sh) {
+  v = wave_max(v);
+  if constexpr (NT == 64) {
+    return v;
+  } else {
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
+  }
+}
+// f(column, logit) for the columns thread t of NT owns: vectors of four from the first aligned element, scalars at the ends
+template <typename T, int NT, typename F>
+__device__ __forceinline__ void soft_ce_each(const T* __restrict__ x, const CeSpan sp, int C, int t, F&& f) {
+  for (int v = t; v < sp.nvec; v += NT) {
+    const int c = sp.head + 4 * v;
+    const float4 q = ld4<T>(x + c);
+    f(c, q.x); f(c + 1, q.y); f(c + 2, q.z); f(c + 3, q.w);
+  }
+  for (int c = t; c < sp.head; c += NT) f(c, io<T>::ld(x + c));
+  for (int c = sp.tail0 + t; c < C; c += NT) f(c, io<T>::ld(x + c));
+}
+
+template <typename T, int NT>
+__global__ __launch_bounds__(256) void soft_ce_fwd_kernel(const T* __restrict__ logits, const float* __restrict__ targets,
+                                                          const int64_t* __restrict__ idx, float* __restrict__ loss,
+                                                          float* __restrict__ stats, int rows, int C) {
+  __shared__ float sh[4];
+  const int row = NT == 64 ? blockIdx.x * 4 + (threadIdx.x >> 6) : blockIdx.x, t = threadIdx.x & (NT - 1);
+  if (row >= rows) return;                       // NT = 64: whole waves leave, nothing below synchronises the workgroup
+  const T* x = logits + (size_t)row * C;
+  const float* tg = targets + (size_t)(idx ? idx[row] : row) * C;
+  const CeSpan sp = ce_span(row, C);
+  float m = -INFINITY;
+  soft_ce_each<T, NT>(x, sp, C, t, [&](int, float v) { m = fmaxf(m, v); });
+  m = row_max<NT>(m, sh);
+  float s = 0.f;
+  soft_ce_each<T, NT>(x, sp, C, t, [&](int, float v) { s += __expf(v - m); });
+  const float ls = __logf(row_sum<NT>(s, sh));
+  float l = 0.f, S = 0.f;
+  soft_ce_each<T, NT>(x, sp, C, t, [&](int c, float v) {
+    const float p = tg[c];
+    S += p;
+    if (p != 0.f) l += p * logf(p) - p * ((v - m) - ls);      // a select: a zero target adds exactly 0
+  });
+  l = row_sum<NT>(l, sh);
+  S = row_sum<NT>(S, sh);
+  if (t == 0) {
+    loss[row] = l;
+    stats[row] = m;
+    stats[rows + row] = ls;
+    stats[2 * rows + row] = S;
+  }
+}
+
+template <typename T, int NT>
+__global__ __launch_bounds__(256) void soft_ce_bwd_kernel(const T* __restrict__ logits, const float* __restrict__ targets,
+                                                          const int64_t* __restrict__ idx, const float* __restrict__ stats,
+                                                          const float* __restrict__ dloss, T* __restrict__ dlogits, int rows,
+                                                          int C) {
+  const int row = NT == 64 ? blockIdx.x * 4 + (threadIdx.x >> 6) : blockIdx.x, t = threadIdx.x & (NT - 1);
+  if (row >= rows) return;
+  const T* x = logits + (size_t)row * C;
+  T* d = dlogits + (size_t)row * C;
+  const float* tg = targets + (size_t)(idx ? idx[row] : row) * C;
+  const CeSpan sp = ce_span(row, C);
+  const float m = stats[row], ls = stats[rows + row], S = stats[2 * rows + row], g = dloss[row];
+  for (int v = t; v < sp.nvec; v += NT) {
+    const int c = sp.head + 4 * v;
+    const float4 q = ld4<T>(x + c);
+    st4<T>(d + c, make_float4((__expf((q.x - m) - ls) * S - tg[c]) * g, (__expf((q.y - m) - ls) * S - tg[c + 1]) * g,
+                              (__expf((q.z - m) - ls) * S - tg[c + 2]) * g, (__expf((q.w - m) - ls) * S - tg[c + 3]) * g));
+  }
+  for (int c = t; c < sp.head; c += NT) io<T>::st(d + c, (__expf((io<T>::ld(x + c) - m) - ls) * S - tg[c]) * g);
+  for (int c = sp.tail0 + t; c < C; c += NT) io<T>::st(d + c, (__expf((io<T>::ld(x + c) - m) - ls) * S - tg[c]) * g);
+}
+
+BEVBERT_API int bevbert_soft_ce_fwd(const void* logits, const float* targets, const int64_t* idx, float* loss, float* stats,
+                                    int rows, int C, int dtype, hipStream_t stream) {
+  BB_REQUIRE(C >= 1, "soft_ce: C=%d", C);
+  if (rows <= 0) return BB_OK;
+  BB_REQUIRE(((uintptr_t)logits % 16) == 0, "soft_ce: logits must be 16-byte aligned%s", "");
+  if (dtype != BB_F32 && dtype != BB_BF16) return bb_dtype_unsupported("soft_ce", dtype);
+  BB_REQUIRE(logits && targets && loss && stats, "soft_ce_fwd: null tensor%s", "");
+  const bool type_ok = bb_with_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (C <= SOFT_CE_WAVE_ROW_MAX)
+      hipLaunchKernelGGL((soft_ce_fwd_kernel<T, 64>), dim3((rows + 3) / 4), dim3(256), 0, stream, (const T*)logits, targets, idx,
+                         loss, stats, rows, C);
+    else
+      hipLaunchKernelGGL((soft_ce_fwd_kernel<T, 256>), dim3(rows), dim3(256), 0, stream, (const T*)logits, targets, idx, loss,
+                         stats, rows, C);
+  });
+  if (!type_ok) return bb_dtype_unsupported("soft_ce", dtype);
+  BB_CHECK_LAUNCH("soft_ce_fwd");
+  return BB_OK;
+}
+
+BEVBERT_API int bevbert_soft_ce_bwd(const void* logits, const float* targets, const int64_t* idx, const float* stats,
+                                    const float* dloss, void* dlogits, int rows, int C, int dtype, hipStream_t stream) {
+  BB_REQUIRE(C >= 1, "soft_ce: C=%d", C);
+  if (rows <= 0) return BB_OK;
+  BB_REQUIRE(((uintptr_t)logits % 16) == 0 && ((uintptr_t)dlogits % 16) == 0,
+             "soft_ce: logits / dlogits must be 16-byte aligned%s", "");
+  if (dtype != BB_F32 && dtype != BB_BF16) return bb_dtype_unsupported("soft_ce", dtype);
+  BB_REQUIRE(logits && targets && stats && dloss && dlogits, "soft_ce_bwd: null tensor%s", "");
+  const bool type_ok = bb_with_type(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (C <= SOFT_CE_WAVE_ROW_MAX)
+      hipLaunchKernelGGL((soft_ce_bwd_kernel<T, 64>), dim3((rows + 3) / 4), dim3(256), 0, stream, (const T*)logits, targets, idx,
+                         stats, dloss, (T*)dlogits, rows, C);
+    else
+      hipLaunchKernelGGL((soft_ce_bwd_kernel<T, 256>), dim3(rows), dim3(256), 0, stream, (const T*)logits, targets, idx, stats,
+                         dloss, (T*)dlogits, rows, C);
+  });
+  if (!type_ok) return bb_dtype_unsupported("soft_ce", dtype);
+  BB_CHECK_LAUNCH("soft_ce_bwd");
   return BB_OK;
 }

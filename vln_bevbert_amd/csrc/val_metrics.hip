@@ -1,7 +1,8 @@
 // Validation metrics of the pre-training tasks (pretrain_src/train_r2r.py:351-510 validate_mlm / _sap / _sem / _masksem,
 // train_reverie_obj.py validate_og), accumulated on the device so that a validation pass reads back ONCE per task:
 //   (a) bevbert_val_ce_rows    sum of cross-entropies, number of arg-max hits and number of rows of (R, C) logits
-//   (b) bevbert_val_bce_keys   sum of BCE-with-logits, number of rows, and one packed sort key per element for the AUC
+//   (a') bevbert_val_kl_rows   sum of KL divergences to soft target rows, arg-max agreements and number of rows (MRC)
+//   (b) bevbert_val_bce_keys  sum of BCE-with-logits, number of rows, and one packed sort key per element for the AUC
 //   (c) bevbert_val_auc        exact Mann-Whitney statistic 2U, P, N of an ascending-sorted key array, in integers
 // Launch-only, caller-owned memory, no atomics: (a) and (b) leave one {value, flags} record per row in scratch, (c) one
 // {sum, P, N} record per workgroup, and a single workgroup folds the records in index order -- two runs give the same
@@ -193,6 +194,86 @@ BEVBERT_API int bevbert_val_ce_rows(const void* logits, int64_t ld, const int64_
   BB_CHECK_LAUNCH("val_ce_rows");
   hipLaunchKernelGGL(val_fold_kernel, dim3(1), dim3(256), 0, stream, rec, R, acc);
   BB_CHECK_LAUNCH("val_ce_rows (fold)");
+  return BB_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// (a') Soft targets (MRC): the row's KL to a row of fp32 probabilities read through an index, and whether the two arg-maxes
+// agree.  Pass one is (a)'s scan of the logits (m, s, arg-max); pass two walks the target row: its arg-max (lowest index on a
+// tie: a thread meets its columns in ascending order) and sum_c xlogy(t, t) - t ((x - m) - log s), formed and summed in fp64
+// from the fp32 statistics m and s, the fp32 difference x - m and the fp32 log t.  The row's sum is then rounded to fp32 once
+// for its ValRow record, as (a)'s row loss is; the fold adds the records in fp64.
+// NT = 64: one wave per row, four rows per workgroup; NT = 256: one workgroup per row.
+struct KlPart { double kl; float best; int idx; };
+__device__ __forceinline__ void kl_merge(KlPart& a, double kl, float best, int idx) {
+  if (best > a.best || (best == a.best && idx < a.idx)) { a.best = best; a.idx = idx; }
+  a.kl += kl;
+}
+
+template <typename T, int NT>
+__global__ __launch_bounds__(256) void val_kl_kernel(const T* __restrict__ x, int64_t ld, const float* __restrict__ targets,
+                                                     const int64_t* __restrict__ idx, const float* __restrict__ valid, int R,
+                                                     int C, ValRow* __restrict__ rec) {
+  __shared__ RowStat part[4];
+  __shared__ KlPart kpart[4];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, t = threadIdx.x & (NT - 1);
+  const int row = NT == 64 ? blockIdx.x * 4 + w : blockIdx.x;
+  if (row >= R) return;                                  // NT = 64: whole waves; nothing below synchronises them
+  if (valid && valid[row] == 0.f) {                      // uniform over the row's threads
+    if (t == 0) rec[row] = ValRow{0.f, 0u};
+    return;
+  }
+  const T* p = x + (size_t)row * ld;
+  const float* tg = targets + (size_t)(idx ? idx[row] : row) * C;
+  RowStat r;
+  stat_init(r);
+  row_scan<T, NT>(p, C, t, r);
+  stat_wave(r);                                          // every lane of the wave holds the wave's statistics
+  if constexpr (NT == 256) {
+    if (lane == 0) part[w] = r;
+    __syncthreads();
+    r = part[0];
+    for (int i = 1; i < 4; ++i) stat_merge(r, part[i].m, part[i].s, part[i].best, part[i].idx);
+  }
+  const float m = r.m;
+  const double ls = log((double)r.s);                    // x - m is exact in fp32 near the maximum; log s and the sum in fp64
+  KlPart k{0.0, -INFINITY, 0x7fffffff};
+  for (int c = t; c < C; c += NT) {
+    const float q = tg[c];
+    if (q > k.best || k.idx == 0x7fffffff) { k.best = q; k.idx = c; }
+    if (q != 0.f) k.kl += (double)q * ((double)logf(q) - ((double)(io<T>::ld(p + c) - m) - ls));
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) kl_merge(k, __shfl_xor(k.kl, o, 64), __shfl_xor(k.best, o, 64), __shfl_xor(k.idx, o, 64));
+  if constexpr (NT == 256) {
+    if (lane == 0) kpart[w] = k;
+    __syncthreads();
+    k = kpart[0];
+    for (int i = 1; i < 4; ++i) kl_merge(k, kpart[i].kl, kpart[i].best, kpart[i].idx);
+  }
+  if (t == 0) rec[row] = ValRow{(float)k.kl, 2u | (r.idx == k.idx ? 1u : 0u)};
+}
+
+BEVBERT_API int bevbert_val_kl_rows(const void* logits, int64_t ld, const float* targets, const int64_t* idx, const float* valid,
+                                    int R, int C, int dtype, void* acc, void* scratch, hipStream_t stream) {
+  BB_REQUIRE(R >= 0 && C >= 1 && ld >= C, "val_kl_rows: R=%d C=%d ld=%lld", R, C, (long long)ld);
+  if (R == 0) return BB_OK;
+  if (dtype != BB_F32 && dtype != BB_BF16) return bb_dtype_unsupported("val_kl_rows", dtype);
+  BB_REQUIRE(logits && targets && acc && scratch, "val_kl_rows: null tensor%s", "");
+  BB_REQUIRE(((uintptr_t)acc & 7) == 0 && ((uintptr_t)scratch & 7) == 0, "val_kl_rows: acc / scratch not 8-byte aligned%s", "");
+  ValRow* rec = static_cast<ValRow*>(scratch);
+  bb_with_type(dtype, [&](auto T_) {
+    using T = decltype(T_);
+    if (C <= VAL_WAVE_ROW_MAX)
+      hipLaunchKernelGGL((val_kl_kernel<T, 64>), dim3((R + 3) / 4), dim3(256), 0, stream, (const T*)logits, ld, targets, idx, valid,
+                         R, C, rec);
+    else
+      hipLaunchKernelGGL((val_kl_kernel<T, 256>), dim3(R), dim3(256), 0, stream, (const T*)logits, ld, targets, idx, valid, R, C,
+                         rec);
+  });
+  BB_CHECK_LAUNCH("val_kl_rows");
+  hipLaunchKernelGGL(val_fold_kernel, dim3(1), dim3(256), 0, stream, rec, R, acc);
+  BB_CHECK_LAUNCH("val_kl_rows (fold)");
   return BB_OK;
 }
 

@@ -15,7 +15,7 @@ is loader work here (``StaticBatch._host_side``), done by the producer thread of
           |<----------------- release(sb): ``done`` event on the compute stream
 
 A bucket is what a hipGraph is captured on: the signature is (task, B, text shape, panorama shape, map width, padded row
-counts); buffer sets of a bucket are separate ``StaticBatch`` objects, each with its own captured step.  Buckets are
+counts; for object-token batches also their object layout -- with ``obj_static=True`` only its padded widths); buffer sets of a bucket are separate ``StaticBatch`` objects, each with its own captured step.  Buckets are
 kept LRU up to ``max_buckets``; what the manager did (buckets created / evicted, refills, bytes copied) is counted so
 that ``bench.py --stream`` can report it.
 """
@@ -42,12 +42,13 @@ class BucketManager:
 
     WAIT_TIMEOUT_S = 120.0       # a consumer that never releases is a bug: say so instead of hanging forever
 
-    def __init__(self, cfg, device, depth=2, max_buckets=16, grid_store=None):
+    def __init__(self, cfg, device, depth=2, max_buckets=16, grid_store=None, obj_static=False):
         device = torch.device(device)
         if device.type == "cuda" and device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
         self.cfg, self.device, self.depth, self.max_buckets = cfg, device, depth, max_buckets
         self.grid_store = grid_store
+        self.obj_static = obj_static        # passed through to StaticBatch: object-token batches padded and capturable
         self.buckets = collections.OrderedDict()        # signature -> {"sets": [StaticBatch], "next": int}
         self.copy_stream_probe = None
         self.copy_stream = pick_copy_stream(self.device, self) if self.device.type == "cuda" else None
@@ -83,7 +84,7 @@ class BucketManager:
         is about to overwrite is still held by the consumer or read by an earlier step; ``stop`` (a threading.Event owned
         by the calling loader) ends such a wait with LoaderStopped."""
         t0 = time.perf_counter()
-        host = StaticBatch.plan(self.cfg, task, batch)
+        host = StaticBatch.plan(self.cfg, task, batch, obj_static=self.obj_static)
         sig = host["signature"]
         b = self.buckets.get(sig)
         if b is None:
@@ -100,7 +101,8 @@ class BucketManager:
         self.buckets.move_to_end(sig)
         if len(b["sets"]) < self.depth:                  # first uses of a bucket: allocate another buffer set
             with self._on_copy_stream():
-                sb = StaticBatch(self.cfg, task, batch, self.device, grid_store=self.grid_store, grid_keys=grid_keys)
+                sb = StaticBatch(self.cfg, task, batch, self.device, grid_store=self.grid_store, grid_keys=grid_keys,
+                                 obj_static=self.obj_static)
                 sb.ready = self._record()
             sb.done = None
             b["sets"].append(sb)

@@ -443,6 +443,40 @@ def cross_entropy_rows(logits, target):
     return torch.nn.functional.cross_entropy(logits.float(), target, reduction="none")
 
 
+class _SoftCE(torch.autograd.Function):
+    """F.kl_div(F.log_softmax(logits.float(), -1), targets[idx], reduction="none").sum(1) without the fp32 copy of the
+    logits and without the gathered copy of the target rows; ``targets`` gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, idx):
+        rows, C = logits.shape
+        logits = logits.contiguous()
+        out = torch.empty(4, rows, dtype=torch.float32, device=logits.device)      # loss | row maximum | log sum exp | sum of t
+        call("bevbert_soft_ce_fwd", ptr(logits), ptr(targets), ptr(idx), ptr(out[0]), ptr(out[1]), rows, C,
+             dtype_code(logits), stream())
+        ctx.save_for_backward(logits, targets, idx, out)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, dloss):
+        logits, targets, idx, out = ctx.saved_tensors
+        rows, C = logits.shape
+        d = torch.empty_like(logits)
+        call("bevbert_soft_ce_bwd", ptr(logits), ptr(targets), ptr(idx), ptr(out[1]), ptr(dloss.contiguous().float()), ptr(d),
+             rows, C, dtype_code(logits), stream())
+        return d, None, None
+
+
+def soft_ce_rows(logits, targets, idx=None):
+    """(rows,) fp32 KL divergences of (rows, C) logits in the compute dtype to the fp32 rows ``targets[idx]`` (``idx``
+    None: row r) -- the MRC head's loss (pretrain_cmt.py:272-297).  There is no torch fallback: a CPU tensor raises."""
+    assert logits.dim() == 2 and targets.dim() == 2 and targets.shape[1] == logits.shape[1]
+    assert targets.dtype == torch.float32 and targets.is_contiguous()
+    assert idx is None or (idx.dtype == torch.int64 and idx.is_contiguous() and idx.numel() == logits.shape[0])
+    assert idx is not None or targets.shape[0] == logits.shape[0]
+    return _SoftCE.apply(logits, targets, idx)
+
+
 # ----------------------------------------------------------------------------- K4 bias + GELU
 class _BiasGelu(torch.autograd.Function):
     """act(x + bias); ``act``: "gelu" (erf) or "relu" -- the C ABI has one entry pair per activation."""

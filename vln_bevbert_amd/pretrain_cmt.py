@@ -275,6 +275,9 @@ class GlocalTextPathCMTPreTraining(nn.Module):
     def _host_kw(self, b):
         kw = {"view_lens_host": b.get("traj_vp_view_lens_cpu"), "obj_lens_host": b.get("traj_vp_obj_lens_cpu"),
               "gmap_csr": b.get("gmap_csr")}
+        st = b.get("_static")
+        if st is not None and "obj_rows" in st:      # loader-built object-token rows (static_step.StaticBatch, obj_static)
+            kw["obj_tables"] = (st["obj_rows"], st["obj_valid"])
         if getattr(self.config, "depth_feat_size", 0) > 0:           # continuous-environment fork
             kw["traj_view_dep_fts"] = b["traj_view_dep_fts"]
         return kw
@@ -282,6 +285,23 @@ class GlocalTextPathCMTPreTraining(nn.Module):
     def forward_mrc(self, b, compute_loss):
         """pretrain_cmt.py:272-297: masked-region classification on the object tokens (KL to detector probs)."""
         _, _, obj_embeds, _ = self.bert(*self._cmt_args(b), return_gmap_embeds=False, **self._host_kw(b))
+        st = b.get("_static")
+        if st is not None and "mrc_pos" in st:
+            # loader-built rows of the masked objects, padded to a fixed count (the padding re-reads row 0 at weight 0), as
+            # the MLM selection below: no nonzero() sync, static shapes, and the KL straight from the head's logits
+            flat = obj_embeds.reshape(-1, obj_embeds.shape[-1])
+            masked = ops.take_rows(flat, st["mrc_pos"]) if flat.is_cuda else flat.index_select(0, st["mrc_pos"])
+            probs = b["vp_obj_probs"].reshape(-1, b["vp_obj_probs"].shape[-1])
+            if compute_loss == "mean" and flat.is_cuda:
+                per_row = ops.soft_ce_rows(self.obj_classifier(masked), probs, st["mrc_tpos"])
+                return ops.weighted_mean(per_row, st["mrc_valid"], st["mrc_n_dev"])     # / masked objects of the batch in the buffers
+            n = st["mrc_n"]
+            pred = self.obj_classifier(masked).float()[:n]
+            targets = probs.index_select(0, st["mrc_tpos"][:n])
+            if compute_loss:
+                loss = F.kl_div(F.log_softmax(pred, dim=-1), targets, reduction="none").sum(dim=1)
+                return loss.mean() if compute_loss == "mean" else loss
+            return pred, targets
         sel = b["vp_obj_mrc_masks"]
         host = b.get("vp_obj_mrc_masks_cpu")
         if host is not None:

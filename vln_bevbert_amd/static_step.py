@@ -8,8 +8,8 @@ joined inside), gradient clipping, AdamW -- with one launch.  Three things make 
   * every quantity that changes from step to step lives in DEVICE memory, not in launch arguments: the dropout salt
     (ops._Runtime / bevbert_set_step_salt) and the learning rate (ParamArena.set_lr);
   * everything the reference builds on the host INSIDE the forward -- positions of the masked tokens, the SAP logit
-    fusion table, the global-map aggregation CSR -- is built by the loader (``StaticBatch``) next to its host->device
-    copies; data-dependent row counts (masked tokens, supervised BEV cells) are padded to a fixed size with
+    fusion table, the global-map aggregation CSR, and with ``obj_static`` the rows of the last panoramas' object tokens
+    and of the masked objects (MRC) -- is built by the loader (``StaticBatch``) next to its host->device copies; data-dependent row counts (masked tokens, supervised BEV cells) are padded to a fixed size with
     zero-weight rows, so the step has no host<->device synchronisation and fixed kernel shapes;
   * a ``StaticBatch`` owns preallocated device buffers of one shape bucket: the loader refills them in place
     (``load``), the graph captured on them is replayed.  Device-resident grid features
@@ -47,6 +47,12 @@ _env_int = lambda k, d: int(__import__("os").environ.get(k, d))
 TXT_PAD = _env_int("BEVBERT_TXT_PAD", 16)
 PANO_PAD = _env_int("BEVBERT_PANO_PAD", 32)
 VIEW_PAD = _env_int("BEVBERT_VIEW_PAD", 4)
+# Object tokens (REVERIE / SOON), opt-in through ``obj_static=True``: the object axis of traj_obj_img_fts and the width O of
+# the last panoramas' object lists (vp_obj_probs, vp_obj_mrc_masks, the OG logits) are rounded up to OBJ_PAD, the joint
+# [views | objects] token axis of traj_loc_fts / traj_nav_types to VIEW_PAD; the rows of the last panoramas' object tokens
+# and of the masked objects (MRC) are loader-built tables, so the step reads nothing from the host and can be captured.
+OBJ_PAD = _env_int("BEVBERT_OBJ_PAD", 4)
+MRC_ROW_PAD = 64        # masked-object rows (15 % of the last panoramas' objects) are padded to a multiple of this
 
 
 def _round_up(n, m):
@@ -56,18 +62,21 @@ def _round_up(n, m):
 class StaticBatch:
     """Device buffers + loader-built index tensors of one batch of one task, in a fixed shape bucket."""
 
-    def __init__(self, cfg, task, batch, device, grid_store=None, grid_keys=None):
+    def __init__(self, cfg, task, batch, device, grid_store=None, grid_keys=None, obj_static=False):
         """``batch``: the collate output on the host (synthetic.collate / the reference's *_collate schema).
         ``grid_store`` + ``grid_keys``: draw the grid features from a device-resident GridFeatureStore instead of
-        shipping ``rgbs`` / ``depths`` / ``sems`` (the keys name the samples' viewpoints)."""
+        shipping ``rgbs`` / ``depths`` / ``sems`` (the keys name the samples' viewpoints).
+        ``obj_static``: pad an object-token batch like any other and ship its object / MRC row tables (see OBJ_PAD)."""
         self.cfg, self.task, self.device = cfg, task, torch.device(device)
+        self.obj_static = bool(obj_static)
         self.graph = None           # set by PretrainTrainer once the step has been captured on these buffers
         self.loss_out = None
         self.eager_runs = 0
         # Object tokens (REVERIE / SOON: traj_obj_img_fts) are gathered with indices the forward derives on the HOST from
         # traj_step_lens / traj_vp_obj_lens (vilmodel._obj_tokens) and uploads inside the forward: a captured graph would
-        # either refuse the pageable copy or freeze the indices of the batch it was captured on.  Such batches run eagerly.
-        self.capturable = batch.get("traj_obj_img_fts") is None
+        # either refuse the pageable copy or freeze the indices of the batch it was captured on.  Such batches run eagerly
+        # -- unless ``obj_static`` moved those indices into loader-built tables (``_host_side``).
+        self.capturable = batch.get("traj_obj_img_fts") is None or self.obj_static
         host = self._host_side(batch)
         self.signature = host["signature"]
         t = {}
@@ -89,11 +98,11 @@ class StaticBatch:
         self._refresh_counts()
 
     @staticmethod
-    def plan(cfg, task, batch):
+    def plan(cfg, task, batch, obj_static=False):
         """The host-side part alone (shape signature, padded tensors, index tables) -- what a loader computes to find
         the bucket of a batch before it touches any device buffer (loader.BucketManager)."""
         self = object.__new__(StaticBatch)
-        self.cfg, self.task = cfg, task
+        self.cfg, self.task, self.obj_static = cfg, task, bool(obj_static)
         return self._host_side(batch)
 
     # -- host side: everything that is a Python loop over ids or a data-dependent count --------------------------
@@ -115,6 +124,7 @@ class StaticBatch:
             pd = full
         padded["gmap_pair_dists"] = pd
         has_obj = batch.get("traj_obj_img_fts") is not None
+        obj_static = has_obj and self.obj_static
         # ---- text width
         L = batch["txt_ids"].shape[1]
         Lp = _round_up(L, TXT_PAD)
@@ -123,24 +133,35 @@ class StaticBatch:
                 if batch.get(k) is not None:
                     padded[k] = torch.cat([batch[k], batch[k].new_full((B, Lp - L), fill)], 1)
         txt_shape = (B, Lp)
-        # ---- panorama count and view count (object-token batches run eagerly anyway: left as they are)
+        # ---- panorama count and view count (object-token batches without ``obj_static`` run eagerly anyway: left as they are)
         view_lens = batch["traj_vp_view_lens"]
+        obj_lens = batch.get("traj_vp_obj_lens")
         T0, V0 = batch["traj_view_img_fts"].shape[:2]
-        Tp, Vp = (T0, V0) if has_obj else (_round_up(T0, PANO_PAD), _round_up(V0, VIEW_PAD))
-        if (Tp, Vp) != (T0, V0):
-            for k in ("traj_view_img_fts", "traj_loc_fts", "traj_nav_types", "traj_view_dep_fts"):
-                v = batch.get(k)
-                if v is None:
-                    continue
-                full = v.new_zeros((Tp, Vp) + tuple(v.shape[2:]))
-                full[:T0, :V0] = v
-                padded[k] = full
+        Tp, Vp = (T0, V0) if has_obj and not obj_static else (_round_up(T0, PANO_PAD), _round_up(V0, VIEW_PAD))
+        n_views = batch["traj_loc_fts"].shape[1] if has_obj else Vp        # objects: the joint [views | objects] token axis
+        widths = {} if has_obj else {k: Vp for k in ("traj_view_img_fts", "traj_loc_fts", "traj_nav_types", "traj_view_dep_fts")}
+        if obj_static:
+            # the object axis and the joint axis are padded like the view axis; dummy panoramas have no objects
+            n_views = _round_up(n_views, VIEW_PAD)
+            Ob = _round_up(max(1, batch["traj_obj_img_fts"].shape[1]), OBJ_PAD)
+            widths.update(traj_view_img_fts=Vp, traj_view_dep_fts=Vp, traj_loc_fts=n_views, traj_nav_types=n_views,
+                          traj_obj_img_fts=Ob)
+        for k, width in widths.items():
+            v = batch.get(k)
+            if v is None or tuple(v.shape[:2]) == (Tp, width):
+                continue
+            full = v.new_zeros((Tp, width) + tuple(v.shape[2:]))
+            full[:T0, :v.shape[1]] = v
+            padded[k] = full
+        if Tp != T0:
             view_lens = torch.cat([view_lens, view_lens.new_ones(Tp - T0)])
             padded["traj_vp_view_lens"] = view_lens
+            if obj_lens is not None:
+                obj_lens = torch.cat([obj_lens, obj_lens.new_zeros(Tp - T0)])
+                padded["traj_vp_obj_lens"] = obj_lens
         lens = view_lens
-        if batch.get("traj_vp_obj_lens") is not None:
-            lens = lens + batch["traj_vp_obj_lens"]
-        n_views = batch["traj_loc_fts"].shape[1] if has_obj else Vp        # objects: the joint [views | objects] token axis
+        if obj_lens is not None:
+            lens = lens + obj_lens
         rowptr, idx, w, n_src, G = gmap_csr_arrays(list(batch["traj_step_lens"]), lens.tolist(), batch["traj_vpids"],
                                                   batch["traj_cand_vpids"], batch["gmap_vpids"], n_views, G)
         n_src = Tp * n_views                       # the dummy panoramas are source rows no segment points at
@@ -160,7 +181,38 @@ class StaticBatch:
         if not has_obj:
             seq_masks(view_lens, Vp, "pano", inf=True)
         sig = [task, B, txt_shape, (Tp, Vp) + tuple(batch["traj_view_img_fts"].shape[2:]), G]
-        if batch.get("traj_obj_img_fts") is not None:      # buffers of a bucket must agree on the object-token layout too
+        if obj_static:
+            # the panorama encoder's masks over the joint axis (hung on traj_vp_view_lens; ImageEmbeddings.embed looks there)
+            seq_masks(lens, n_views, "pano", inf=True)
+            # object tokens of every sample's LAST panorama (vilmodel._obj_tokens): token view_len + j of panorama ends[b] as a
+            # flat row of the (Tp * n_views, H) panorama states; invalid entries read row 0 and are masked
+            ends = torch.from_numpy(np.cumsum(list(batch["traj_step_lens"])) - 1)
+            vl_e, ol_e = view_lens[ends], obj_lens[ends]
+            Op = _round_up(max(1, int(ol_e.max())), OBJ_PAD)
+            j = torch.arange(Op)[None, :]
+            valid = j < ol_e[:, None]
+            rows = ends[:, None] * n_views + vl_e[:, None] + j
+            static["obj_rows"] = torch.where(valid, rows, torch.zeros_like(rows)).reshape(-1).contiguous()
+            static["obj_valid"] = valid
+            for k in ("vp_obj_probs", "vp_obj_mrc_masks"):      # (B, O, ...) -> (B, Op, ...)
+                v = batch.get(k)
+                if v is not None and v.shape[1] != Op:
+                    full = v.new_zeros((B, Op) + tuple(v.shape[2:]))
+                    full[:, :v.shape[1]] = v
+                    padded[k] = full
+            sig.append(("obj", Ob, int(n_views), Op, int(getattr(cfg, "obj_prob_size", 0))))
+            if task.startswith("mrc"):
+                # rows of the masked objects, in the (B * Op, H) object states and in the flattened vp_obj_probs (the two
+                # agree while both are padded to Op), padded to a fixed count with row 0 at weight 0 -- as mlm_pos below
+                pos = torch.nonzero(padded.get("vp_obj_mrc_masks", batch["vp_obj_mrc_masks"]).reshape(-1)).squeeze(1)
+                n = int(pos.numel())
+                npad = _round_up(max(n, 1), MRC_ROW_PAD)
+                static["mrc_n"] = n
+                static["mrc_pos"] = torch.cat([pos, pos.new_zeros(npad - n)])
+                static["mrc_tpos"] = static["mrc_pos"].clone()
+                static["mrc_valid"] = (torch.arange(npad) < n).to(torch.float32)
+                sig.append(npad)
+        elif has_obj:                                      # buffers of a bucket must agree on the object-token layout too
             # (incl. the width of the joint [views | objects] token axis: the maximum of views + objects over the panoramas)
             sig.append(("obj", tuple(batch["traj_obj_img_fts"].shape), tuple(int(x) for x in batch["traj_step_lens"]),
                         int(n_views)))
@@ -265,6 +317,10 @@ class StaticBatch:
             if "mlm_n_dev" not in st:
                 st["mlm_n_dev"] = torch.zeros((), dtype=torch.float32, device=self.device)
             st["mlm_n_dev"].fill_(float(st["mlm_n"]))
+        if "mrc_n" in st:
+            if "mrc_n_dev" not in st:
+                st["mrc_n_dev"] = torch.zeros((), dtype=torch.float32, device=self.device)
+            st["mrc_n_dev"].fill_(float(st["mrc_n"]))
 
 
 class GraphedStep:

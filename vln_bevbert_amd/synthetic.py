@@ -58,9 +58,11 @@ def _mask_tokens(rng, ids, vocab_lo, vocab_hi, mask_id):
     return out, lab
 
 
-def make_sample(rng, i, cfg, n_steps, txt_len, ragged_views=False, grid=True):
+def make_sample(rng, i, cfg, n_steps, txt_len, ragged_views=False, grid=True, max_objects=None):
     """One sample in the schema of ``get_input`` + the task Dataset ``__getitem__``.  ``grid=False``: without the grid
-    features / depths / class ids (samples whose grid features live in a device-resident feature_store.GridFeatureStore)."""
+    features / depths / class ids (samples whose grid features live in a device-resident feature_store.GridFeatureStore).
+    ``max_objects``: draw 0 .. max_objects objects per panorama (the reference's ``max_objects`` is 20); None keeps the
+    historical counts (0 .. 4 on ragged views, else 3)."""
     bev_dim = cfg.bev_dim
     n_cells = bev_dim * bev_dim
     hw = cfg.grid_hw
@@ -100,7 +102,10 @@ def make_sample(rng, i, cfg, n_steps, txt_len, ragged_views=False, grid=True):
             dep_fts.append(rng.standard_normal((nv, dep_size)).astype(np.float32))
         nt = [1] * len(cands[t]) + [0] * (nv - len(cands[t]))
         if has_obj:     # REVERIE: object tokens follow the views (dataset.py:283-321): loc = [angle(4), box(3)], type 2
-            no = int(rng.integers(0, 5)) if ragged_views else 3
+            if max_objects is not None:
+                no = int(rng.integers(0, max_objects + 1))
+            else:
+                no = int(rng.integers(0, 5)) if ragged_views else 3
             if t == n_steps - 1 and no == 0 and i % 2 == 0:
                 no = 2          # most samples end on a viewpoint with objects; odd ones may have none
             obj_fts.append(rng.standard_normal((no, cfg.obj_feat_size)).astype(np.float32))
@@ -288,14 +293,14 @@ def collate(samples, cfg, task, rng, sems_as="onehot64"):
 
 
 def make_batch(cfg, task, batch_size, seed=1000, txt_len=80, n_steps=5, ragged=False,
-               sems_as="onehot64"):
+               sems_as="onehot64", max_objects=None):
     """Seeded batch. ``ragged``: T_i in [1,7], text lens in [L/2, L], 36..38 views."""
     rng = np.random.default_rng(seed)
     samples = []
     for i in range(batch_size):
         T = int(rng.integers(1, 8)) if ragged else n_steps
         L = int(rng.integers(txt_len // 2, txt_len + 1)) if ragged else txt_len
-        samples.append(make_sample(rng, i, cfg, T, L, ragged_views=ragged))
+        samples.append(make_sample(rng, i, cfg, T, L, ragged_views=ragged, max_objects=max_objects))
     return collate(samples, cfg, task, rng, sems_as=sems_as)
 
 

@@ -7,6 +7,8 @@ counts and the sort keys of the AUC stay in device memory (csrc/val_metrics.hip)
 
 Metric definitions ("Validation metrics"):
   * mlm, og:        loss = sum of cross-entropies / rows, acc = arg-max hits / rows (lowest index on a tie).
+  * mrc:            loss = sum over the masked objects of KL(detector probabilities || softmax(logits)) / objects, acc =
+                    objects whose arg-max class equals the arg-max of their probabilities / objects (lowest index on a tie).
   * sap:            gloss / lloss / floss and gacc / lacc / facc over the global, local and fused logits, all divided by
                     the number of samples; a label of -100 adds no loss and no hit but counts as a sample.
   * sem, masksem:   loss = sum of BCE-with-logits over all elements / ROWS (the reference's divisor), auc = the exact
@@ -62,6 +64,23 @@ def val_ce_rows(logits, targets, valid, acc):
          dtype_code(logits), ptr(acc), ptr(_scratch(logits.device, 8 * R)), stream())
 
 
+def val_kl_rows(logits, targets, idx, valid, acc):
+    """acc (fp64 KL sum, arg-max agreements, rows) += the rows of ``logits`` (R, C) fp32 / bf16 against the fp32 rows
+    ``targets[idx]`` (idx None: row r); see include/bevbert_hip.h bevbert_val_kl_rows."""
+    assert logits.dim() == 2 and logits.stride(1) == 1 and targets.dim() == 2 and targets.shape[1] == logits.shape[1]
+    assert targets.dtype == torch.float32 and targets.is_contiguous()
+    R, C = logits.shape
+    assert (idx is None and targets.shape[0] == R) or (idx is not None and idx.dtype == torch.int64 and idx.is_contiguous()
+                                                       and idx.numel() == R)
+    assert valid is None or (valid.dtype == torch.float32 and valid.is_contiguous() and valid.numel() == R)
+    assert acc.dtype == torch.int64 and acc.numel() == 3 and acc.is_contiguous()
+    if TAP is not None:
+        TAP.append(("val_kl_rows", {"logits": logits.clone(), "targets": targets.clone(), "idx": None if idx is None else idx.clone(),
+                                    "valid": None if valid is None else valid.clone()}))
+    call("bevbert_val_kl_rows", ptr(logits), logits.stride(0) if R > 1 else C, ptr(targets), ptr(idx), ptr(valid), R, C,
+         dtype_code(logits), ptr(acc), ptr(_scratch(logits.device, 8 * R)), stream())
+
+
 def val_bce_keys(logits, labels, idx, valid, acc, keys, cursor, capacity, overflow):
     """acc += (BCE sum, valid rows); keys[cursor : cursor + R C] = the packed sort keys (INT64_MAX for invalid rows);
     returns the advanced cursor.  ``labels`` uint8 (n, C) read through ``idx`` (None: row r)."""
@@ -113,6 +132,9 @@ class ValAccumulator:
 
     def add_ce(self, logits, targets, valid=None, which=0):
         val_ce_rows(logits, targets, valid, self.acc(which))
+
+    def add_kl(self, logits, targets, idx=None, valid=None):
+        val_kl_rows(logits, targets, idx, valid, self.acc(0))
 
     def add_bce(self, logits, labels, idx=None, valid=None):
         need = self.cursor + logits.numel()
@@ -193,6 +215,17 @@ def add_batch(model, task, batch, acc):
     elif task.startswith("og"):
         b = batch.tensors if isinstance(batch, StaticBatch) else batch
         acc.add_ce(model(b, task, compute_loss=False), b["obj_labels"].contiguous())
+    elif task.startswith("mrc") and isinstance(batch, StaticBatch) and "mrc_pos" in batch.tensors["_static"]:
+        # an obj_static batch: loader-built rows of the masked objects, zero-weight padding, no synchronisation
+        b = _static_inputs(model, batch)
+        st = b["_static"]
+        _, _, obj, _ = model.bert(*model._cmt_args(b), return_gmap_embeds=False, **model._host_kw(b))
+        rows = ops.take_rows(obj.reshape(-1, obj.shape[-1]), st["mrc_pos"])
+        probs = b["vp_obj_probs"].reshape(-1, b["vp_obj_probs"].shape[-1])
+        acc.add_kl(model.obj_classifier(rows), probs, st["mrc_tpos"], st["mrc_valid"])      # logits in the compute dtype
+    elif task.startswith("mrc"):
+        pred, targets = model(batch.tensors if isinstance(batch, StaticBatch) else batch, task, compute_loss=False)
+        acc.add_kl(pred, targets.contiguous())                                          # one sync, as the reference
     elif task.startswith(("sem", "masksem")):
         logits, labels = model(batch, task, compute_loss=False)
         acc.add_bce(logits, (labels != 0).to(torch.uint8).contiguous())
@@ -206,6 +239,9 @@ def val_log(task, r, seconds):
     if task.startswith(("mlm", "og")):
         n = r["b"][0]
         return {"loss": div(r["sums"][0], n), "acc": div(r["a"][0], n), "tok_per_s": n / seconds}
+    if task.startswith("mrc"):          # train_reverie_obj.py:415-446: KL sum and arg-max agreements over the masked objects
+        n = r["b"][0]
+        return {"loss": div(r["sums"][0], n), "acc": div(r["a"][0], n), "feat_per_s": n / seconds}
     if task.startswith("sap"):
         n = r["b"][0]
         return {"gloss": div(r["sums"][0], n), "lloss": div(r["sums"][1], n), "floss": div(r["sums"][2], n),
@@ -225,7 +261,7 @@ def validate(model, val_loaders, setname="", key_capacity=None, raw=None):
     try:
         dev = next(model.parameters()).device
         for task, loader in val_loaders.items():
-            if not task.startswith(("mlm", "sap", "og", "sem", "masksem")):
+            if not task.startswith(("mlm", "mrc", "sap", "og", "sem", "masksem")):
                 raise ValueError(f"Undefined task {task}")
             acc = ValAccumulator(dev, key_capacity)
             acc.reset()

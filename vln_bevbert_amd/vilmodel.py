@@ -566,7 +566,11 @@ class ImageEmbeddings(nn.Module):
         fuse_drop = self.pano_encoder is not None and self.training and self.drop_p > 0 and e.is_cuda
         if not fuse_drop:
             e = ops.dropout(e, self.drop_p, self.training)
-        masks = gen_seq_masks(lens, e.shape[1])
+        # with objects ``lens`` is a sum made here: a loader that pads object batches (static_step.StaticBatch, obj_static)
+        # hangs the masks of the joint axis on view_lens, where it hangs the view masks of a batch without objects
+        masks = getattr(view_lens, "_seq_masks", None)
+        if masks is None or masks.shape[1] != e.shape[1]:
+            masks = gen_seq_masks(lens, e.shape[1])
         if self.pano_encoder is not None:
             km = getattr(masks, "_km_inf", None)          # loader-built (static_step.StaticBatch)
             e = self.pano_encoder(e, None if km is not None else masks.logical_not(), key_mask=km,
@@ -795,10 +799,18 @@ class GlocalTextPathCMT(nn.Module):
         ol = _host_list(obj_lens_host if obj_lens_host is not None else traj_vp_obj_lens)
         return [a + b for a, b in zip(vl, ol)], ol
 
-    def _obj_tokens(self, traj, traj_step_lens, traj_vp_view_lens, traj_vp_obj_lens, obj_lens_host):
-        """vilmodel.py:748-756: the object tokens of every sample's LAST panorama, zero padded, + validity mask."""
+    def _obj_tokens(self, traj, traj_step_lens, traj_vp_view_lens, traj_vp_obj_lens, obj_lens_host, obj_tables=None):
+        """vilmodel.py:748-756: the object tokens of every sample's LAST panorama, zero padded, + validity mask.
+        ``obj_tables``: (obj_rows (B * O) int64 flat rows into the (T * L, H) panorama states, obj_valid (B, O) bool) built
+        by the loader (static_step.StaticBatch, obj_static): nothing is derived on the host or uploaded here then, and the
+        mask zeroes the invalid rows and their gradient."""
         if traj_vp_obj_lens is None:
             return None, None
+        if obj_tables is not None:
+            rows, valid = obj_tables
+            flat = traj.reshape(-1, traj.shape[-1])
+            obj = ops.take_rows(flat, rows) if flat.is_cuda else flat.index_select(0, rows)
+            return obj.view(valid.shape[0], valid.shape[1], -1) * valid[..., None].to(obj.dtype), valid
         ends_host = np.cumsum(traj_step_lens) - 1
         O = max(1, max(obj_lens_host[e] for e in ends_host))
         ends = torch.from_numpy(ends_host).to(traj.device, non_blocking=True)
@@ -830,7 +842,7 @@ class GlocalTextPathCMT(nn.Module):
                 traj_step_lens, traj_vp_view_lens, traj_vp_obj_lens, traj_vpids, traj_cand_vpids,
                 gmap_lens, gmap_step_ids, gmap_pos_fts, gmap_pair_dists, gmap_vpids,
                 bev_fts, bev_pos_fts, bev_masks, bev_nav_masks, return_gmap_embeds=True, view_lens_host=None,
-                obj_lens_host=None, gmap_csr=None, traj_view_dep_fts=None):
+                obj_lens_host=None, gmap_csr=None, traj_view_dep_fts=None, obj_tables=None):
         has_obj = traj_obj_img_fts is not None
         br = ops.Branches(txt_ids.device)
         gmap_embeds = obj_embeds = obj_masks = traj = None
@@ -858,7 +870,7 @@ class GlocalTextPathCMT(nn.Module):
         if has_obj:             # the object tokens feed the BEV branch: they are needed on the current stream
             br.join(traj)
             obj_embeds, obj_masks = self._obj_tokens(traj, traj_step_lens, traj_vp_view_lens, traj_vp_obj_lens,
-                                                     ol_host)
+                                                     ol_host, obj_tables)
         # side stream: global-map encoder (tiny kernels);  current stream: BEV encoder (28 224-row kernels)
         if return_gmap_embeds:
             br.fork(txt_embeds, txt_masks, gmap_step_ids, gmap_pos_fts, gmap_lens, gmap_pair_dists, traj)
@@ -877,7 +889,7 @@ class GlocalTextPathCMT(nn.Module):
                     traj_step_lens, traj_vp_view_lens, traj_vp_obj_lens, traj_vpids, traj_cand_vpids,
                     gmap_lens, gmap_step_ids, gmap_pos_fts, gmap_pair_dists, gmap_vpids,
                     bev_fts, bev_pos_fts, bev_masks, bev_nav_masks, view_lens_host=None, obj_lens_host=None,
-                    gmap_csr=None, traj_view_dep_fts=None):
+                    gmap_csr=None, traj_view_dep_fts=None, obj_tables=None):
         br = ops.Branches(txt_ids.device)
         br.fork(traj_view_img_fts, traj_loc_fts, traj_nav_types, traj_vp_view_lens, traj_obj_img_fts, traj_vp_obj_lens,
                 traj_view_dep_fts, bev_fts, bev_pos_fts, bev_nav_masks, gmap_step_ids, gmap_pos_fts, gmap_lens)
@@ -913,7 +925,8 @@ class GlocalTextPathCMT(nn.Module):
         obj_embeds = obj_masks = None
         if traj_obj_img_fts is not None:
             br.join(traj)
-            obj_embeds, obj_masks = self._obj_tokens(traj, traj_step_lens, traj_vp_view_lens, traj_vp_obj_lens, ol_host)
+            obj_embeds, obj_masks = self._obj_tokens(traj, traj_step_lens, traj_vp_view_lens, traj_vp_obj_lens, ol_host,
+                                                     obj_tables)
         bev_in, bev_obj_masks = self.local_encoder.with_objects(bev_in, _all_ones_to_none(bev_masks), obj_embeds,
                                                                 obj_masks)
         bev_in = bev_in.contiguous()
@@ -926,7 +939,7 @@ class GlocalTextPathCMT(nn.Module):
                     traj_step_lens, traj_vp_view_lens, traj_vp_obj_lens, traj_vpids, traj_cand_vpids,
                     gmap_lens, gmap_step_ids, gmap_pos_fts, gmap_pair_dists, gmap_vpids,
                     bev_fts, bev_pos_fts, bev_masks, bev_nav_masks, sem_pred_token=None, view_lens_host=None,
-                    obj_lens_host=None, gmap_csr=None, traj_view_dep_fts=None):
+                    obj_lens_host=None, gmap_csr=None, traj_view_dep_fts=None, obj_tables=None):
         bm = _all_ones_to_none(bev_masks)
         if sem_pred_token == "cattn":
             txt_embeds, txt_masks = self._text(txt_ids, txt_lens)
@@ -936,7 +949,7 @@ class GlocalTextPathCMT(nn.Module):
                                   traj_obj_img_fts, traj_vp_obj_lens, traj_view_dep_fts)
                 _, ol_host = self._token_lens_host(traj_vp_view_lens, traj_vp_obj_lens, view_lens_host, obj_lens_host)
                 obj_embeds, obj_masks = self._obj_tokens(traj, traj_step_lens, traj_vp_view_lens, traj_vp_obj_lens,
-                                                         ol_host)
+                                                         ol_host, obj_tables)
             # (without objects the reference still runs img_embeddings here, vilmodel.py:847-851, but nothing consumes it)
             bev_embeds, _ = self.local_encoder(txt_embeds, txt_masks, bev_fts, bev_pos_fts, bm, bev_nav_masks,
                                                obj_embeds, obj_masks)
