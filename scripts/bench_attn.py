@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of the attention C-ABI entry points at the shapes of one R2R pre-training step (B = 64).
-Prints one line per (shape, dropout) with fwd / bwd time and algorithmic TFLOP/s.  Tile-shape knobs are read from the
-environment by the library (BEVBERT_FWD_QT / BEVBERT_DQ_QT / BEVBERT_DKV_KT), so run one process per variant."""
+Prints one line per (shape, dropout) with fwd / bwd time and algorithmic TFLOP/s.  Which kernels run is the library's
+dispatch plan under the BEVBERT_ATTN_* switches of the environment (README.md), read per call."""
 import json
 import os
 import sys

@@ -42,11 +42,9 @@ def main():
         call("bevbert_attn_fwd", ptr(q), ptr(k), ptr(v), ptr(o), ptr(lse), ptr(km), None, st, B, nh, Lq, Lk, 64, scale,
              dtype_code(q), 2, p, 1, 0, ptr(bits), 1, stream())
 
-    trace = torch.zeros(8 * 16 * 8, dtype=torch.int64, device=dev) if os.environ.get("BEVBERT_B2_TRACE") == "1" else None
-
     def bwd():
         call("bevbert_attn_bwd", ptr(q), ptr(k), ptr(v), ptr(o), ptr(do), ptr(lse), ptr(delta), ptr(dq), ptr(dk),
-             ptr(dv), ptr(trace), ptr(km), None, st, B, nh, Lq, Lk, 64, scale, dtype_code(q), 2, p, 1, 0, ptr(bits), stream())
+             ptr(dv), None, ptr(km), None, st, B, nh, Lq, Lk, 64, scale, dtype_code(q), 2, p, 1, 0, ptr(bits), stream())
 
     def timeit(fn):
         for _ in range(3):
@@ -69,15 +67,6 @@ def main():
     t = timeit(bwd)
     out["bwd_us"], out["bwd_tflops"], out["bwd_frac"] = round(t, 1), round(2.5 * fl / t / 1e6, 1), round(2.5 * fl / t / 1e6 / 2500, 4)
     print(json.dumps(out), flush=True)
-    if trace is not None:
-        t = trace.cpu().view(8, 16, 8).numpy()
-        t0 = int(t[:, 0, 0][t[:, 0, 0] > 0].min())
-        print("# workgroup 0: s_memtime stamps relative to the first, per wave (rows) and step; slots 0..4 = step start, "
-              "[dQ wave: loads issued | key waves: -], [dQ done | S/dP/softmax done], [tile committed | dK/dV done], barrier passed")
-        for w_ in range(8):
-            for st_ in range(0, 14):
-                row = t[w_, st_]
-                print(f"wave {w_} step {st_:2d}: " + " ".join(f"{int(x) - t0:8d}" if x else "       -" for x in row[:8]))
 
 
 if __name__ == "__main__":

@@ -4,7 +4,11 @@ directories and compares, kernel symbol by kernel symbol, the instruction text (
 dropped) and the scalar fields of the code-object notes (VGPR / SGPR / AGPR counts, scratch, LDS, max_flat_workgroup_size,
 kernarg size, spill counts).  Prints one line per kernel that changed its object file or differs, one line per object
 whose kernels all stayed and are identical, and exits 1 on any lost, new, duplicated or differing kernel.
-usage: scripts/kernel_identity.py BEFORE/_obj AFTER/_obj"""
+Kernels are matched by demangled name.  --rename REGEX=REPL (repeatable) rewrites the BEFORE names first, for a kernel that
+lost a template argument; a renamed kernel is compared without the .symbol note field, which carries the name.
+--lost-ok REGEX (repeatable): a BEFORE kernel without a partner whose name matches is printed as retired, not as a finding.
+usage: scripts/kernel_identity.py [--rename REGEX=REPL]... [--lost-ok REGEX]... BEFORE/_obj AFTER/_obj"""
+import argparse
 import glob
 import os
 import re
@@ -59,20 +63,39 @@ def kernels_of(objdir):
     return found, dup
 
 
-def main(before_dir, after_dir):
+def main(before_dir, after_dir, renames=(), lost_ok=()):
     (before, dup_b), (after, dup_a) = kernels_of(before_dir), kernels_of(after_dir)
     names = sorted(set(before) | set(after))
     short = dict(zip(names, run("c++filt", input="\n".join(names)).splitlines()))
-    bad, stayed = 0, {}
+    bad, stayed, retired, renamed = 0, {}, 0, set()
     for s in dup_b + dup_a:
         bad += 1
         print(f"DUPLICATED across objects ({'before' if s in dup_b else 'after'}): {short[s]}")
-    for s in names:
+
+    def new_name(name):
+        for pattern, repl in renames:
+            name = re.sub(pattern, repl, name)
+        return name
+
+    n_before = len(before)
+    before = {new_name(short[s]): v for s, v in before.items()}
+    after = {short[s]: v for s, v in after.items()}
+    if len(before) != n_before:
+        bad += 1
+        print(f"--rename maps {n_before - len(before)} BEFORE kernels onto the name of another one")
+    for s in sorted(set(before) | set(after)):
         if s not in before or s not in after:
+            if s in before and any(re.search(p, s) for p in lost_ok):
+                retired += 1
+                print(f"retired: {s}")
+                continue
             bad += 1
-            print(f"{'NEW' if s not in before else 'LOST'}: {short[s]}")
+            print(f"{'NEW' if s not in before else 'LOST'}: {s}")
             continue
         (ob, tb, mb), (oa, ta, ma) = before[s], after[s]
+        if mb.get("symbol") != ma.get("symbol"):        # only a renamed kernel: the field carries the mangled name
+            mb, ma = ({k: v for k, v in m.items() if k != "symbol"} for m in (mb, ma))
+            renamed.add(s)
         same_text, same_meta = tb == ta and len(tb) > 0, mb == ma and len(mb) > 0
         if ob == oa and same_text and same_meta:
             stayed[oa] = stayed.get(oa, 0) + 1
@@ -80,7 +103,7 @@ def main(before_dir, after_dir):
         verdict = "identical" if same_text and same_meta else "DIFFERS:" + " text" * (not same_text) + " notes" * (not same_meta)
         bad += verdict != "identical"
         res = " ".join(f"{mb.get(f, '?')}/{ma.get(f, '?')}" for f in FIELDS)
-        print(f"{short[s].replace('void ', '')}\n    {ob} -> {oa}  insns {len(tb)}/{len(ta)}  {res}  {verdict}")
+        print(f"{s.replace('void ', '')}{' (renamed)' * (s in renamed)}\n    {ob} -> {oa}  insns {len(tb)}/{len(ta)}  {res}  {verdict}")
         if not same_text:
             for i, (x, y) in enumerate(zip(tb, ta)):
                 if x != y:
@@ -88,11 +111,15 @@ def main(before_dir, after_dir):
                     break
     for o in sorted(stayed):
         print(f"{o}: {stayed[o]} kernels stayed, text and notes identical")
-    print(f"{len(before)} kernels before, {len(after)} after, {bad} findings")
+    print(f"{len(before)} kernels before, {len(after)} after, {retired} retired, {len(renamed)} renamed, {bad} findings")
     return 1 if bad else 0
 
 
 if __name__ == "__main__":
-    if len(sys.argv) != 3:
-        sys.exit(__doc__)
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    ap = argparse.ArgumentParser(usage=__doc__)
+    ap.add_argument("--rename", action="append", default=[], metavar="REGEX=REPL")
+    ap.add_argument("--lost-ok", action="append", default=[], metavar="REGEX")
+    ap.add_argument("before")
+    ap.add_argument("after")
+    args = ap.parse_args()
+    sys.exit(main(args.before, args.after, [r.split("=", 1) for r in args.rename], args.lost_ok))

@@ -178,6 +178,10 @@ def boundary_indices(Lk):
 
 
 # ----------------------------------------------------------------------------- the case table
+# Every environment switch the attention sources read (AttnKnobs in capi.hip, and the workgroup count of attn_fwd4.hip):
+# tests clear all of them before they set their own; tests/test_host_logic.py holds the sources and README.md to this list.
+ATTN_KNOBS = ("BEVBERT_ATTN_FWD", "BEVBERT_ATTN_BWD", "BEVBERT_ATTN_BWD3", "BEVBERT_ATTN_SMALL", "BEVBERT_ATTN_SMALL_BWD",
+              "BEVBERT_ATTN_SHORT", "BEVBERT_ATTN_FWD4", "BEVBERT_ATTN_F32", "BEVBERT_FWD4_WGS")
 Case = collections.namedtuple("Case", "B nh Lq Lk dtype impl mask bias p bits knobs fwd bwd")
 _A = "attn_"
 SHORT0, SMALL1, FWD1, BWD1, BWD3_0 = ({"BEVBERT_ATTN_SHORT": "0"}, {"BEVBERT_ATTN_SMALL": "1"}, {"BEVBERT_ATTN_FWD": "1"},

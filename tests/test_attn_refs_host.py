@@ -5,7 +5,7 @@ import pytest
 import torch
 
 from tests import attn_cases as ac
-from tests.test_host_logic import ATTN_KNOBS, attn_plan
+from tests.test_host_logic import attn_plan
 from vln_bevbert_amd import lib
 
 KERNELS = ("attn_short_fwd", "attn_small_fwd", "attn_fwd4", "attn_fwd2", "attn_mfma_fwd", "attn_f32_fwd", "attn_simple_fwd",
@@ -128,7 +128,7 @@ def _rows_of(name):
 
 def test_case_table_is_what_the_plan_says_and_covers_every_kernel_and_length(monkeypatch):
     l = lib.load()
-    assert set(ATTN_KNOBS) >= {k for c in ac.CASES for k in c.knobs}
+    assert set(ac.ATTN_KNOBS) >= {k for c in ac.CASES for k in c.knobs}
     for c in ac.CASES:
         assert attn_plan(l, ac.plan_row(c), 256, monkeypatch) == (c.fwd, c.bwd), ac.case_id(c)
     assert len({ac.case_id(c) for c in ac.CASES}) == len(ac.CASES)

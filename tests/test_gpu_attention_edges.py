@@ -54,8 +54,7 @@ def per_kernel():
 
 
 def _set_knobs(monkeypatch, knobs):
-    from tests.test_host_logic import ATTN_KNOBS
-    for name in ATTN_KNOBS:
+    for name in ac.ATTN_KNOBS:
         monkeypatch.delenv(name, raising=False)
     for name, value in knobs.items():
         monkeypatch.setenv(name, value)

@@ -11,6 +11,7 @@ reference, then dx / dW / db against fp64 GEMMs OF THAT BUFFER), so no bound is 
 import pytest
 import torch
 
+from tests.attn_cases import ATTN_KNOBS
 from tests.test_gpu_kernels import _attn_ref, _make_attn_inputs, ops, rel_err  # noqa: F401  (ops: the module's fixture)
 
 pytestmark = pytest.mark.gpu
@@ -248,8 +249,6 @@ ATTN_GLUE_CASES = {
     "f32_bias":    (23, 23, 23, True, F32, 0, 0.0, {}, "attn_f32_fwd", "attn_f32_bwd"),
     "simple":      (23, 17, 17, False, BF16, 1, 0.1, {}, "attn_simple_fwd", "attn_simple_bwd"),
 }
-ATTN_KNOBS = ("BEVBERT_ATTN_FWD", "BEVBERT_ATTN_BWD", "BEVBERT_ATTN_BWD3", "BEVBERT_ATTN_SMALL", "BEVBERT_ATTN_SMALL_BWD",
-              "BEVBERT_ATTN_SHORT", "BEVBERT_ATTN_FWD4", "BEVBERT_ATTN_F32", "BEVBERT_FWD4_WGS")
 ATTN_SEED = 777
 SENTINEL = 7.0
 

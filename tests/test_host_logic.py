@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from oracle import bevbert_ref as R
+from tests.attn_cases import ATTN_KNOBS
 from tests.helpers import read_shapes
 from vln_bevbert_amd import lib, synthetic
 from vln_bevbert_amd.config import BevBertConfig
@@ -133,8 +134,24 @@ ATTN_PLAN_ROWS = [
     (2, 80, 80, "f32", 0, False, 0.0, "none", {"BEVBERT_ATTN_F32": "simple"}, "simple_fwd", "simple_bwd"),
     (2, 80, 80, "bf16", 1, False, 0.0, "none", {}, "simple_fwd", "simple_bwd"),
 ]
-ATTN_KNOBS = ("BEVBERT_ATTN_FWD", "BEVBERT_ATTN_BWD", "BEVBERT_ATTN_BWD3", "BEVBERT_ATTN_SMALL", "BEVBERT_ATTN_SMALL_BWD",
-              "BEVBERT_ATTN_SHORT", "BEVBERT_ATTN_FWD4", "BEVBERT_ATTN_F32", "BEVBERT_FWD4_WGS")
+
+
+def test_attention_sources_read_only_the_listed_switches():
+    """The dispatch plan is the whole rule: the only environment switches the attention sources and the C ABI name are the
+    ones in ATTN_KNOBS (each read per call, each with plan rows above or cases in tests/attn_cases.py), and README.md's
+    table documents every one.  A switch added without both fails here."""
+    csrc = os.path.join(os.path.dirname(lib.__file__), "csrc")
+    paths = [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if re.fullmatch(r"attn_\w+\.(hip|h)|capi\.hip", f)]
+    assert len(paths) >= 14, paths
+    found = set()
+    for path in paths:
+        with open(path) as f:
+            found |= set(re.findall(r'"(BEVBERT_[A-Z0-9_]+)"', f.read()))
+    assert found == set(ATTN_KNOBS), sorted(found ^ set(ATTN_KNOBS))
+    with open(os.path.join(os.path.dirname(os.path.dirname(lib.__file__)), "README.md")) as f:
+        table = [line for line in f if line.lstrip().startswith("|")]
+    for name in ATTN_KNOBS:
+        assert any(f"`{name}`" in line for line in table), f"README.md's environment table has no row for {name}"
 
 
 def attn_plan(l, row, ncu, monkeypatch):

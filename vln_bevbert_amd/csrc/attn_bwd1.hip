@@ -4,11 +4,10 @@
 // Q, K, V, dO twice: 7 tile GEMMs and ~2x the softmax arithmetic for 5 GEMMs' worth of algorithmic work, on kernels that
 // are VALU-bound.  Here a workgroup owns ALL keys of one (batch, head) (Lk <= 64 * KT <= 448: the 21x21 BEV has 441 cells):
 //
-//   * NW waves; wave w owns the 16*KT keys [w*16*KT, (w+1)*16*KT): its V fragments (B operand of dP) and its dK^T / dV^T
-//     accumulators [64 d][16*KT keys] stay in registers for the whole kernel.  Default geometry: NW = 4, one wave per
-//     SIMD with the whole 512-entry register file (KT = 7: 224 accumulator + 56 operand registers).  An NW = 8 x 64-key
-//     form (two waves per SIMD) exists behind BEVBERT_BWD1_WAVES=8; it has to re-read every fragment per key tile to fit
-//     256 registers and measured slower;
+//   * four waves; wave w owns the 16*KT keys [w*16*KT, (w+1)*16*KT): its V fragments (B operand of dP) and its dK^T / dV^T
+//     accumulators [64 d][16*KT keys] stay in registers for the whole kernel: one wave per SIMD with the whole 512-entry
+//     register file (KT = 7: 224 accumulator + 56 operand registers).  Eight waves of 64 keys (two per SIMD) have to
+//     re-read every fragment per key tile to fit 256 registers and were slower (tried and dropped);
 //   * K is staged once, row-major, in LDS: B operand of S = Q K^T by plain 16-byte reads, and -- through the
 //     transposing LDS read of gfx950 (ds_read_b64_tr_b16) -- the K^T A operand of dQ^T = K^T dS^T from the SAME image;
 //   * loop over 64-query tiles: S and dP on the matrix cores, then ONE pass of softmax-backward arithmetic per score
@@ -37,18 +36,18 @@ template <int NKT> struct B1Lds {
   static constexpr int bytes = stat_off + 2 * TK * 4;
 };
 
-// KT: 16-key tiles per wave; NW: waves per workgroup (4 or 8); NKT: 64-key tiles of the workgroup (LDS images)
+// KT: 16-key tiles per wave; NKT: 64-key tiles of the workgroup (LDS images) = KT with four waves
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // KMASK: an additive key mask exists (a.key_mask).  Without one the scores need no mask term at all: keys beyond Lk have
 // zero K rows in LDS (their dS rows meet zeros in the dQ product) and their dK / dV rows are never stored.
-template <int KT, int NW, int NKT, bool BIAS, bool DROP, bool EARLY, bool KMASK>
-__global__ __launch_bounds__(64 * NW, (NW == 8 || (KT <= 2 && !BIAS)) ? 2 : 1) void attn_mfma_bwd1_kernel(AttnArgs a) {
+template <int KT, int NKT, bool BIAS, bool DROP, bool KMASK>
+__global__ __launch_bounds__(256, (KT <= 2 && !BIAS) ? 2 : 1) void attn_mfma_bwd1_kernel(AttnArgs a) {
   typedef B1Lds<NKT> L;
-  constexpr int NT = 64 * NW;             // threads
-  constexpr int CPT = 512 / NT;           // 16-byte chunks of a [64][64] bf16 tile per thread (2 or 1)
-  constexpr bool HOLD = (NW == 4 && KT >= 4);   // keep the fragments of a half in registers across the key tiles
-  //                                             (short key sequences: two workgroups per CU matter more than LDS reads)
+  constexpr int NT = 256;                 // threads
+  constexpr int CPT = 512 / NT;           // 16-byte chunks of a [64][64] bf16 tile per thread
+  constexpr bool HOLD = KT >= 4;          // keep the fragments of a half in registers across the key tiles
+  //                                         (short key sequences: two workgroups per CU matter more than LDS reads)
   extern __shared__ __attribute__((aligned(16))) unsigned char b1_smem[];
   bf16_raw* const s_q = reinterpret_cast<bf16_raw*>(b1_smem + L::q_off);
   bf16_raw* const s_do = reinterpret_cast<bf16_raw*>(b1_smem + L::do_off);
@@ -77,7 +76,10 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 || (KT <= 2 && !BIAS)) ? 2 : 1) v
 
   // ---- per-wave key state: V fragments, additive key mask (log2 domain; -inf beyond Lk), accumulators
   const int key0 = w * (16 * KT);                  // first key of this wave
-  const bool has_keys = key0 < L::NK;              // NW = 8 on 448 keys: the eighth wave only stages tiles and computes dQ
+  // Always true (four waves, 64 * NKT = 4 * 16 * KT keys).  The compiler cannot see that, and every instantiation's code
+  // changes when the test goes (KT = 7 with dropout and a mask: 3 535 instead of 3 664 instructions), so it stays until a
+  // change that measures the difference takes it out together with the phase-2 tile_issue below.
+  const bool has_keys = key0 < L::NK;
   bf16x8 vf[KT][2];
   float mask2[KT];
 #pragma unroll
@@ -181,9 +183,9 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 || (KT <= 2 && !BIAS)) ? 2 : 1) v
     const bool more = q0 + TK < a.Lq;
 #pragma unroll 1
     for (int m = 0; m < (has_keys ? 2 : 0); ++m) {       // halves of 32 queries: query tiles t = 2m, 2m + 1
-      // EARLY: the next tile's global loads go out under this tile's arithmetic (KT = 7: under its second half, the
+      // the next tile's global loads go out under this tile's arithmetic (KT = 7: under its second half, the
       // registers are full before) instead of under the short dQ phase
-      if (EARLY && m == (KT == 7 ? 1 : 0) && more) tile_issue(q0 + TK);
+      if (m == (KT == 7 ? 1 : 0) && more) tile_issue(q0 + TK);
       bf16x8 qa[2][2], da[2][2], qtf[HOLD ? 4 : 1], dotf[HOLD ? 4 : 1];
       float lv[2][4], ndl[2][4];
       auto load_rows = [&]() {          // A operands of S / dP (rows of this half's two query tiles) and their statistics
@@ -224,7 +226,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 || (KT <= 2 && !BIAS)) ? 2 : 1) v
 #pragma unroll
       for (int kt = 0; kt < KT; ++kt) {
         const int ktg = w * KT + kt;                 // 16-key tile index within the (batch, head)
-        if (!HOLD) load_rows();                      // two waves per SIMD: re-read per key tile, keep the registers free
+        if (!HOLD) load_rows();                      // two workgroups per CU: re-read per key tile, keep the registers free
         f32x4 sacc[2], dpacc[2];
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) {
@@ -329,10 +331,10 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 || (KT <= 2 && !BIAS)) ? 2 : 1) v
     __syncthreads();   // dS image complete; nobody reads s_q / s_do / stats / bits of this tile any more
 
     // ================= phase 2: next tile's loads in flight, dQ^T = K^T dS^T for d rows 16 w .. 16 w + 15 =================
-    if (more && !(EARLY && has_keys)) tile_issue(q0 + TK);
-    // NW = 4: wave w -> d rows 16 w .. +15, all four query tiles;  NW = 8: d rows 16 (w & 3), query tiles 2 (w >> 2), +1
-    constexpr int NQT = (NW == 4) ? 4 : 2;
-    const int dq_d0 = 16 * (w & 3), dq_qt0 = (NW == 4) ? 0 : 2 * (w >> 2);
+    if (more && !has_keys) tile_issue(q0 + TK);     // never taken: see has_keys
+    // wave w -> d rows 16 w .. +15, all four query tiles
+    constexpr int NQT = 4;
+    const int dq_d0 = 16 * (w & 3);     // w < 4; the mask saves the compiler the proof (see has_keys)
     f32x4 dqacc[NQT];
 #pragma unroll
     for (int qt = 0; qt < NQT; ++qt) dqacc[qt] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -341,7 +343,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 || (KT <= 2 && !BIAS)) ? 2 : 1) v
       const bf16x8 ka = lds_frag_tr(s_k, LDT, 32 * ks + 8 * g, 32 * ks + 8 * g + 4, dq_d0, lane);
 #pragma unroll
       for (int qt = 0; qt < NQT; ++qt) {
-        const bf16x8 dsf = lds_frag_tr(s_ds, B1_LDS_DS, 32 * ks + 8 * g, 32 * ks + 8 * g + 4, 16 * (dq_qt0 + qt), lane);
+        const bf16x8 dsf = lds_frag_tr(s_ds, B1_LDS_DS, 32 * ks + 8 * g, 32 * ks + 8 * g + 4, 16 * qt, lane);
         dqacc[qt] = mfma16(ka, dsf, dqacc[qt]);
       }
     }
@@ -352,7 +354,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 || (KT <= 2 && !BIAS)) ? 2 : 1) v
     // lane (query = q0 + 16 qt + c) holds dQ^T[d = dq_d0 + 4 g + r][query]
 #pragma unroll
     for (int qt = 0; qt < NQT; ++qt) {
-      const int qi = q0 + (dq_qt0 + qt) * 16 + c;
+      const int qi = q0 + qt * 16 + c;
       if (qi < a.Lq) {
         bf16_raw* dqp = (bf16_raw*)a.dq + (size_t)b * a.bsq + (size_t)qi * a.ldq + h * ATTN_D + dq_d0 + 4 * g;
         st4<bf16_raw>(dqp, make_float4(dqacc[qt][0] * dq_scale, dqacc[qt][1] * dq_scale, dqacc[qt][2] * dq_scale,
@@ -385,38 +387,27 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 || (KT <= 2 && !BIAS)) ? 2 : 1) v
 // =============================================================================================
 // launcher
 // =============================================================================================
-template <int KT, int NW, int NKT, bool B_, bool D_, bool E_, bool M_>
+template <int KT, int NKT, bool B_, bool D_, bool M_>
 static int launch_bwd1(const AttnArgs& a, hipStream_t st) {
   typedef B1Lds<NKT> L;
   static const bool ok =
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_mfma_bwd1_kernel<KT, NW, NKT, B_, D_, E_, M_>),
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_mfma_bwd1_kernel<KT, NKT, B_, D_, M_>),
                           hipFuncAttributeMaxDynamicSharedMemorySize, L::bytes) == hipSuccess;
   BB_REQUIRE(ok, "attention bwd (single pass): cannot raise the dynamic LDS limit to %d bytes", L::bytes);
-  hipLaunchKernelGGL((attn_mfma_bwd1_kernel<KT, NW, NKT, B_, D_, E_, M_>), dim3((unsigned)a.B * a.nh), dim3(64 * NW),
-                     L::bytes, st, a);
+  hipLaunchKernelGGL((attn_mfma_bwd1_kernel<KT, NKT, B_, D_, M_>), dim3((unsigned)a.B * a.nh), dim3(256), L::bytes, st, a);
   BB_CHECK_LAUNCH("attn_bwd(single pass)");
   return BB_OK;
 }
 
-template <int KT, int NW, int NKT>
+template <int KT, int NKT>
 static int dispatch_bwd1(const AttnArgs& a, hipStream_t st) {
   const bool hb = a.bias != nullptr, hd = a.drop_p > 0.f, km = a.key_mask != nullptr;
-  // BEVBERT_BWD1_EARLY=0: issue the next query tile's loads only in the dQ phase (A/B knob for the 448-key form)
-  static const bool late = [] { const char* v = getenv("BEVBERT_BWD1_EARLY"); return v && v[0] == '0'; }();
   if constexpr (NKT <= 2) {      // the additive graph bias only occurs on the global map (a few dozen nodes)
-    if (hb && hd) return launch_bwd1<KT, NW, NKT, true, true, true, true>(a, st);
-    if (hb) return launch_bwd1<KT, NW, NKT, true, false, true, true>(a, st);
+    if (hb && hd) return launch_bwd1<KT, NKT, true, true, true>(a, st);
+    if (hb) return launch_bwd1<KT, NKT, true, false, true>(a, st);
   }
-  if constexpr (KT == 7) {
-    if (late) {
-      if (hd) return launch_bwd1<KT, NW, NKT, false, true, false, true>(a, st);
-      return launch_bwd1<KT, NW, NKT, false, false, false, true>(a, st);
-    }
-  }
-  if (hd) return km ? launch_bwd1<KT, NW, NKT, false, true, true, true>(a, st)
-                    : launch_bwd1<KT, NW, NKT, false, true, true, false>(a, st);
-  return km ? launch_bwd1<KT, NW, NKT, false, false, true, true>(a, st)
-            : launch_bwd1<KT, NW, NKT, false, false, true, false>(a, st);
+  if (hd) return km ? launch_bwd1<KT, NKT, false, true, true>(a, st) : launch_bwd1<KT, NKT, false, true, false>(a, st);
+  return km ? launch_bwd1<KT, NKT, false, false, true>(a, st) : launch_bwd1<KT, NKT, false, false, false>(a, st);
 }
 
 // The single-pass kernel covers Lk <= 448 (a bias: Lk <= 128) and, with dropout, needs the forward's keep-bit matrix;
@@ -427,15 +418,8 @@ bool attn_mfma_bwd1_supported(const AttnArgs& a) {
 
 int attn_mfma_bwd1(const AttnArgs& a, hipStream_t st) {
   BB_REQUIRE(attn_mfma_operands_aligned(a, true), "attention bwd (MFMA path): " ATTN_MFMA_ALIGN_MSG);
-  // BEVBERT_BWD1_WAVES=8: 8 waves x 64 keys (two waves per SIMD, no fragments held in registers) instead of 4 x 112.
-  // Measured on the BEV shape (B = 64, 441 x 441, p = 0.1, same box): 303 us vs 262 us -- the re-read fragments cost more
-  // LDS time than the second wave hides, so one wave per SIMD is the default.
-  static const bool eight = [] { const char* v = getenv("BEVBERT_BWD1_WAVES"); return v && v[0] == '8'; }();
-  if (a.Lk <= 64) return dispatch_bwd1<1, 4, 1>(a, st);
-  // 65..128 keys (the 80 text tokens): BEVBERT_BWD1_KEYS128=8 -> eight waves of 16 keys instead of four of 32
-  static const bool k128_8 = [] { const char* v = getenv("BEVBERT_BWD1_KEYS128"); return v && v[0] == '8'; }();
-  if (a.Lk <= 128) return k128_8 ? dispatch_bwd1<1, 8, 2>(a, st) : dispatch_bwd1<2, 4, 2>(a, st);
-  if (a.Lk <= 256) return dispatch_bwd1<4, 4, 4>(a, st);
-  if (eight) return dispatch_bwd1<4, 8, 7>(a, st);
-  return dispatch_bwd1<7, 4, 7>(a, st);
+  if (a.Lk <= 64) return dispatch_bwd1<1, 1>(a, st);
+  if (a.Lk <= 128) return dispatch_bwd1<2, 2>(a, st);       // the 80 text tokens
+  if (a.Lk <= 256) return dispatch_bwd1<4, 4>(a, st);
+  return dispatch_bwd1<7, 7>(a, st);
 }

@@ -24,15 +24,7 @@
 // Covers 256 < Lk <= 448 without a per-element bias (the BEV encoder's 441 cells); everything else stays on attn_bwd1.
 #include "attn_bwd7p1.h"
 
-// BEVBERT_B2_TRACE=1 (bench_attn_shape.py passes a scratch buffer as dbias): workgroup 0 stamps s_memtime per wave, step
-// and phase into it -- the phase timeline of profiles/r03*_bwd2_timeline*.txt.  Compiled out otherwise.
-#define B2_STAMP(step, slot)                                                                         \
-  do {                                                                                               \
-    if (TRACE && bh == 0 && lane == 0 && (step) < 16)                                                \
-      reinterpret_cast<unsigned long long*>(a.dbias)[(w * 16 + (step)) * 8 + (slot)] = __builtin_amdgcn_s_memtime(); \
-  } while (0)
-
-template <bool DROP, bool KMASK, bool TRACE>
+template <bool DROP, bool KMASK>
 __global__ __launch_bounds__(512, 2) void attn_bwd2_kernel(AttnArgs a) {
   typedef B2Lds L;
   extern __shared__ __attribute__((aligned(16))) unsigned char b2_smem[];
@@ -193,15 +185,10 @@ __global__ __launch_bounds__(512, 2) void attn_bwd2_kernel(AttnArgs a) {
       }
     for (int k = 0; k < nsteps; ++k) {
       const bool more = k + 1 < nsteps;
-      B2_STAMP(k, 0);
       if (more) tile_issue(32 * (k + 1));
-      B2_STAMP(k, 1);
       if (k > 0) dq_step(32 * (k - 1), (k - 1) & 1);
-      B2_STAMP(k, 2);
       if (more) tile_commit((k + 1) & 1);
-      B2_STAMP(k, 3);
       __syncthreads();                                 // closes step k
-      B2_STAMP(k, 4);
     }
     dq_step(32 * (nsteps - 1), (nsteps - 1) & 1);
     return;
@@ -255,7 +242,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd2_kernel(AttnArgs a) {
     const bf16_raw* tdo = s_do + buf * (32 * LDT);
     const float* st = s_stat + buf * 64;
     bf16_raw* img = s_ds + buf * (B2_NK * B2_LDS_DS);
-    B2_STAMP(k, 0);
     if (has_keys) {
       // A operands of S / dP: the rows of both query tiles, read once per step
       bf16x8 qa[2][2], da[2][2];
@@ -273,7 +259,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd2_kernel(AttnArgs a) {
         nl[tt][0] = -l4.x; nl[tt][1] = -l4.y; nl[tt][2] = -l4.z; nl[tt][3] = -l4.w;      // -lse (log2 domain)
         ndl[tt] = (f32x4){-d4.x, -d4.y, -d4.z, -d4.w};                                     // -delta / ks
       }
-      B2_STAMP(k, 1);
 #pragma unroll
       for (int kt = 0; kt < 4; ++kt) {
         const bf16x8 vf0 = vf[kt][0], vf1 = vf[kt][1];
@@ -295,7 +280,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd2_kernel(AttnArgs a) {
           dpacc[tt] = mfma16(da[tt][0], vf0, DROP ? (f32x4){0.f, 0.f, 0.f, 0.f} : ndl[tt]);
           dpacc[tt] = mfma16(da[tt][1], vf1, dpacc[tt]);
         }
-        if (kt == 0) B2_STAMP(k, 5);
         uint2 dsu[2], pdu[2];
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) {
@@ -318,7 +302,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd2_kernel(AttnArgs a) {
           // dS image [key][query]: this lane's 4 consecutive queries of tile tt at row key
           *reinterpret_cast<uint2*>(img + (key0 + kt * 16 + c) * B2_LDS_DS + 16 * tt + 4 * g) = dsu[tt];
         }
-        if (kt == 0) B2_STAMP(k, 6);
         // B operands of the "contract over queries" products: k-slot (g, j) <-> query 16 (j >> 2) + 4 g + (j & 3)
         const bf16x8 dsb = as_bf16x8(make_uint4(dsu[0].x, dsu[0].y, dsu[1].x, dsu[1].y));
         const bf16x8 pdb = as_bf16x8(make_uint4(pdu[0].x, pdu[0].y, pdu[1].x, pdu[1].y));
@@ -335,13 +318,9 @@ __global__ __launch_bounds__(512, 2) void attn_bwd2_kernel(AttnArgs a) {
 #pragma unroll
           for (int i = 0; i < 8; ++i) bw[i] = bwn[i];
         }
-        if (kt == 0) B2_STAMP(k, 7);
-        if (kt == 1) B2_STAMP(k, 2);
       }
     }
-    B2_STAMP(k, 3);
     __syncthreads();                                     // closes step k
-    B2_STAMP(k, 4);
   }
 
   // ---- epilogue: dK = scale * ks * dK^T, dV = ks * dV^T
@@ -366,12 +345,12 @@ __global__ __launch_bounds__(512, 2) void attn_bwd2_kernel(AttnArgs a) {
 // =============================================================================================
 // launcher
 // =============================================================================================
-template <bool D_, bool M_, bool T_ = false>
+template <bool D_, bool M_>
 static int launch_bwd2(const AttnArgs& a, hipStream_t st) {
-  static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd2_kernel<D_, M_, T_>),
+  static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd2_kernel<D_, M_>),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, B2Lds::bytes) == hipSuccess;
   BB_REQUIRE(ok, "attention bwd (7+1 waves): cannot raise the dynamic LDS limit to %d bytes", B2Lds::bytes);
-  hipLaunchKernelGGL((attn_bwd2_kernel<D_, M_, T_>), dim3((unsigned)a.B * a.nh), dim3(512), B2Lds::bytes, st, a);
+  hipLaunchKernelGGL((attn_bwd2_kernel<D_, M_>), dim3((unsigned)a.B * a.nh), dim3(512), B2Lds::bytes, st, a);
   BB_CHECK_LAUNCH("attn_bwd(7+1 waves)");
   return BB_OK;
 }
@@ -383,8 +362,6 @@ bool attn_bwd2_supported(const AttnArgs& a) {
 int attn_bwd2(const AttnArgs& a, hipStream_t st) {
   BB_REQUIRE(attn_mfma_operands_aligned(a, true), "attention bwd (MFMA path): " ATTN_MFMA_ALIGN_MSG);
   const bool hd = a.drop_p > 0.f, km = a.key_mask != nullptr;
-  static const bool trace = [] { const char* v = getenv("BEVBERT_B2_TRACE"); return v && v[0] == '1'; }();
-  if (trace && a.dbias != nullptr && hd && !km) return launch_bwd2<true, false, true>(a, st);
   if (hd) return km ? launch_bwd2<true, true>(a, st) : launch_bwd2<true, false>(a, st);
   return km ? launch_bwd2<false, true>(a, st) : launch_bwd2<false, false>(a, st);
 }

@@ -27,9 +27,7 @@
 // Covers what attn_bwd2.hip covers (no per-element bias, 256 < Lk <= 448); BEVBERT_ATTN_BWD3=0 selects the round-3 kernel.
 #include "attn_bwd7p1.h"
 
-// ABL (diagnostics, BEVBERT_B3_ABL; results are WRONG with any bit set): 1 = no dK / dV products, 2 = no dQ products,
-// 4 = no softmax arithmetic, 8 = no tile staging after tile 0
-template <bool DROP, bool KMASK, int ABL>
+template <bool DROP, bool KMASK>
 __global__ __launch_bounds__(512, 2) void attn_bwd3_kernel(AttnArgs a) {
   typedef B2Lds L;
   extern __shared__ __attribute__((aligned(16))) unsigned char b3_smem[];
@@ -140,7 +138,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd3_kernel(AttnArgs a) {
       if (i == 3 && lane < 32) st[lane] = lreg * LOG2E;
     };
     auto dq_step = [&](int q0, int buf) __attribute__((always_inline)) {
-      if (ABL & 2) return;
       const bf16_raw* img = s_ds + buf * (B2_NK * B2_LDS_DS);
       f32x4 dqacc[2][4];
 #pragma unroll
@@ -186,7 +183,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd3_kernel(AttnArgs a) {
         kres[i][dt] = lds_frag_tr(s_k, LDT, 32 * ks + 8 * g, 32 * ks + 8 * g + 4, 16 * dt, lane);
       }
     for (int k = 0; k < nsteps; ++k) {
-      const bool more = k + 1 < nsteps && !(ABL & 8);
+      const bool more = k + 1 < nsteps;
       if (more) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) issue_piece(i, 32 * (k + 1));
@@ -246,11 +243,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd3_kernel(AttnArgs a) {
   // softmax backward of one chain (key tile x 16-query tile): 4 score elements per lane, P / dS stay in their lanes
   auto soft_bwd = [&](const f32x4& sacc, const f32x4& dpacc, const float (&nl)[4], const f32x4& ndl, float mk,
                       const uint64_t* bwords, uint2& dsu, uint2& pdu) __attribute__((always_inline)) {
-    if (ABL & 4) {
-      dsu = make_uint2(__float_as_uint(sacc[0]), __float_as_uint(dpacc[1]));
-      pdu = make_uint2(__float_as_uint(sacc[2]), __float_as_uint(dpacc[3]));
-      return;
-    }
     // Two elements per instruction where the operation allows (v_pk_fma_f32 / v_pk_mul_f32: the accumulator quad is two
     // register pairs): scale-and-shift, P delta, and the final multiply-add -- 1.5 instead of 3 instruction slots per
     // element; the exponential and the keep select stay per element.
@@ -336,7 +328,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd3_kernel(AttnArgs a) {
         for (int tt = 0; tt < 2; ++tt)
           *reinterpret_cast<uint2*>(img + (key0 + kt * 16 + c) * B2_LDS_DS + 16 * tt + 4 * g) = dsu[kt][tt];
 #pragma unroll
-      for (int dt = 0; dt < ((ABL & 1) ? 0 : 4); ++dt) {
+      for (int dt = 0; dt < 4; ++dt) {
         bf16x8 fqn = fq, fdon = fdo;
         if (dt < 3) {
           fqn = lds_frag_tr(tq, LDT, 4 * g, 16 + 4 * g, (dt + 1) * 16, lane);
@@ -404,12 +396,12 @@ __global__ __launch_bounds__(512, 2) void attn_bwd3_kernel(AttnArgs a) {
 // =============================================================================================
 // launcher
 // =============================================================================================
-template <bool D_, bool M_, int A_ = 0>
+template <bool D_, bool M_>
 static int launch_bwd3(const AttnArgs& a, hipStream_t st) {
-  static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd3_kernel<D_, M_, A_>),
+  static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd3_kernel<D_, M_>),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, B2Lds::bytes) == hipSuccess;
   BB_REQUIRE(ok, "attention bwd (7+1 waves, gen 3): cannot raise the dynamic LDS limit to %d bytes", B2Lds::bytes);
-  hipLaunchKernelGGL((attn_bwd3_kernel<D_, M_, A_>), dim3((unsigned)a.B * a.nh), dim3(512), B2Lds::bytes, st, a);
+  hipLaunchKernelGGL((attn_bwd3_kernel<D_, M_>), dim3((unsigned)a.B * a.nh), dim3(512), B2Lds::bytes, st, a);
   BB_CHECK_LAUNCH("attn_bwd(7+1 waves, gen 3)");
   return BB_OK;
 }
@@ -421,19 +413,6 @@ bool attn_bwd3_supported(const AttnArgs& a) {
 int attn_bwd3(const AttnArgs& a, hipStream_t st) {
   BB_REQUIRE(attn_mfma_operands_aligned(a, true), "attention bwd (MFMA path): " ATTN_MFMA_ALIGN_MSG);
   const bool hd = a.drop_p > 0.f, km = a.key_mask != nullptr;
-  static const int abl = [] { const char* v = getenv("BEVBERT_B3_ABL"); return v ? atoi(v) : 0; }();
-  if (abl && hd && !km) {
-    switch (abl) {
-      case 1: return launch_bwd3<true, false, 1>(a, st);
-      case 2: return launch_bwd3<true, false, 2>(a, st);
-      case 4: return launch_bwd3<true, false, 4>(a, st);
-      case 8: return launch_bwd3<true, false, 8>(a, st);
-      case 10: return launch_bwd3<true, false, 10>(a, st);
-      case 11: return launch_bwd3<true, false, 11>(a, st);
-      case 15: return launch_bwd3<true, false, 15>(a, st);
-      default: break;
-    }
-  }
   if (hd) return km ? launch_bwd3<true, true>(a, st) : launch_bwd3<true, false>(a, st);
   return km ? launch_bwd3<false, true>(a, st) : launch_bwd3<false, false>(a, st);
 }

@@ -1,5 +1,5 @@
 // Shared by the two generations of the 7 + 1-wave single-pass backward (attn_bwd2.hip: round 3, attn_bwd3.hip: round 5):
-// LDS map, keep-bit select, the DPP row sum.
+// LDS map, the packed bf16 dot product.
 #pragma once
 #include "attn_mfma_common.h"
 
@@ -15,22 +15,6 @@ struct B2Lds {
   static constexpr int stat_off = do_off + 2 * 32 * LDT * 2;        // [2][2][32] float  lse (log2 domain), delta / ks
   static constexpr int bytes = stat_off + 2 * 2 * 32 * 4;
 };
-
-typedef const __attribute__((address_space(4))) uint64_t* bb_cu64p;
-__device__ __forceinline__ float keep_select(float p, uint64_t lane_mask) {
-  return __builtin_amdgcn_inverse_ballot_w64(lane_mask) ? p : 0.f;     // one v_cndmask_b32 with an SGPR-pair condition
-}
-
-// sum over the 8 lanes that share a tile row (lanes 8 j .. 8 j + 7) on the DPP network: no LDS round trip
-template <int CTRL> __device__ __forceinline__ float dpp_f32(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float sum8(float v) {
-  v += dpp_f32<0xB1>(v);      // quad_perm [1,0,3,2]
-  v += dpp_f32<0x4E>(v);      // quad_perm [2,3,0,1]
-  return v + dpp_f32<0x141>(v);   // row_half_mirror: lane i <-> 7 - i of its half row
-}
-
 
 // a.lo * b.lo + a.hi * b.hi + acc on two packed bf16 pairs (v_dot2c_f32_bf16): products exact in fp32, fp32 accumulation
 typedef __bf16 bb_bf16pair __attribute__((ext_vector_type(2)));

@@ -46,8 +46,12 @@ struct AttnArgs {
   void *dq, *dk, *dv;      // same strides as q/k/v
   float* dbias;            // (B, nh, Lq, Lk) fp32 per-head bias gradients (every element written once, no atomics; the
                            // caller folds the heads in a fixed order), or null
-  int dbg;                 // timing ablations of attn_short.hip (BEVBERT_SHORT_DBG; results WRONG): 1 no output stores, 2 no O loads
+  // Not read by anything: keeps the struct at 256 bytes.  With 248 the kernel-argument segments are 8 bytes shorter and the
+  // latency-bound short kernels start later -- attn_short_fwd at B = 64, 80 x 80: 8.79 - 8.83 against 8.60 - 8.62 us with
+  // the same instructions (profiles/r11a_attn_short_kernarg_size_probe.jsonl)
+  uint64_t pad_to_256;
 };
+static_assert(sizeof(AttnArgs) == 256, "see pad_to_256");
 
 // What the bf16 kernels ask of their operands: 16-byte vector loads and stores of rows of 64 bf16 -- every pointer 16-byte
 // aligned, every stride a multiple of 8 elements; the gradients (backward) share the strides of q / k / v / o.

@@ -12,23 +12,13 @@
 //     pair, the same counter-based stream as every other dropout site) as 64-bit lane masks in exactly the layout of the
 //     S accumulators.  The forward fetches them with scalar loads (constant address space -> s_load_dwordx16) and drops
 //     with ONE v_cndmask_b32 per element (SGPR-pair condition); 1 / (1 - p) is folded into the final normalisation;
-//   * workgroups of NW waves x 32 queries: NW = 7 covers the 441 BEV cells in two workgroups of 224 queries with 1.6 %
-//     padding (the 128-query blocks of round 2 wasted 14 % of the grid); 32-key halves keep the kernel at <= 128 VGPRs so
-//     that two 7-wave workgroups share a CU (3.5 waves per SIMD).
+//   * workgroups of 4 waves x 32 queries; 32-key halves keep the kernel at <= 128 VGPRs so that four workgroups share a
+//     CU (16 waves).  Workgroups of 7 waves (two cover the 441 BEV cells with 1.6 % padding) were slower: DESIGN.md.
 // Per score element: max3 (1/2), fma, exp2, add, cndmask (dropout only), cvt_pk (1/2)  =  4 - 5 vector instructions per
 // matrix instruction.
 #include "attn_mfma_common.h"
 
 #define FWD2_THR 5.0f
-
-typedef const __attribute__((address_space(4))) uint64_t* bb_cu64p;   // uniform loads through the scalar cache
-
-// keep ? p : 0 with the keep decisions of the 64 lanes in a scalar register pair: one v_cndmask_b32 (the compiler sees
-// the instruction, so the transcendental-result hazard behind v_exp_f32 is padded by it, unlike inside inline asm)
-__device__ __forceinline__ float drop_select(float p, uint64_t lane_mask) {
-  return __builtin_amdgcn_inverse_ballot_w64(lane_mask) ? p : 0.f;
-}
-__device__ __forceinline__ float max3f(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
 
 // K / V tiles of this kernel: [64 rows][64 bf16] at a row stride of 72 elements (144 B).  Measured on the MI355X at
 // B = 64, 441 x 441 (gpurun_out r03d / r03k / r03l): 144-byte rows with four 4-wave workgroups per CU 87.7 / 76.4 us
@@ -38,6 +28,7 @@ __device__ __forceinline__ float max3f(float a, float b, float c) { return fmaxf
 // Occupancy beats bank conflicts here: LDS is busy a quarter of the time, the waves wait on latency.
 #define F2_LD 72
 #define F2_TILE (TK * F2_LD)
+#define F2_NW 4       // waves per workgroup, 32 queries each
 __device__ __forceinline__ int f2_off(int row, int chunk) { return row * F2_LD + (chunk << 3); }
 __device__ __forceinline__ bf16x8 f2_frag_rows(const bf16_raw* tile, int t, int ks, int lane) {
   return as_bf16x8(*reinterpret_cast<const uint4*>(tile + f2_off(t * 16 + (lane & 15), ks * 4 + (lane >> 4))));
@@ -51,212 +42,16 @@ __device__ __forceinline__ bf16x8 f2_frag_tr(const bf16_raw* img, int row_lo, in
   return as_bf16x8(make_uint4(lo.x, lo.y, hi.x, hi.y));
 }
 
-template <int NW, bool DROP>
-__global__ __launch_bounds__(64 * NW, 4) void attn_fwd2_kernel(AttnArgs a) {
+// (Named fwd3: the round-3 kernel of this file on a further diet -- fused multiply-add before the maximum, select before
+// the packed conversion, keep-bit words of a whole tile requested in front of the tile barrier; see the comments inside.)
+template <bool DROP>
+__global__ __launch_bounds__(64 * F2_NW, 4) void attn_fwd3_kernel(AttnArgs a) {
+  constexpr int NW = F2_NW;
   constexpr int QT = 2;                      // 16-query tiles per wave
   constexpr int NT = 64 * NW;
-  constexpr int CPT = (512 + NT - 1) / NT;   // 16-byte chunks of a [64][64] bf16 tile per thread
-  __shared__ __attribute__((aligned(16))) bf16_raw s_k[2][F2_TILE];
-  __shared__ __attribute__((aligned(16))) bf16_raw s_v[2][F2_TILE];
-  __shared__ __attribute__((aligned(16))) float s_mask[2][TK];
-  const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c = lane & 15;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  int blk, h, b;
-  attn_decode_block(a, blk, h, b);
-  const int qbase = blk * (16 * QT * NW) + w * (16 * QT);
-  const bf16_raw* qp = (const bf16_raw*)a.q + (size_t)b * a.bsq + h * ATTN_D;
-  const bf16_raw* kp = (const bf16_raw*)a.k + (size_t)b * a.bsk + h * ATTN_D;
-  const bf16_raw* vp = (const bf16_raw*)a.v + (size_t)b * a.bsv + h * ATTN_D;
-  const float sc2 = a.scale * LOG2E;
-  const float inv_scale = 1.0f / a.scale;
-
-  bf16x8 qf[QT][2];
-  int qrow[QT];
-#pragma unroll
-  for (int qt = 0; qt < QT; ++qt) {
-    qrow[qt] = qbase + qt * 16 + c;
-    const int r = qrow[qt] < a.Lq ? qrow[qt] : a.Lq - 1;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) qf[qt][ks] = as_bf16x8(ld_frag_global(qp, a.ldq, r, ks * 32 + g * 8));
-  }
-  // keep-bit words of this wave's query tiles: 16 words (t, r) per (query tile, 64-key tile), 64-key tiles contiguous
-  bb_cu64p wq[QT];
-  if (DROP) {
-#pragma unroll
-    for (int qt = 0; qt < QT; ++qt) {
-      int q16 = (qbase >> 4) + qt;
-      q16 = q16 < a.nq16 ? q16 : a.nq16 - 1;       // query tiles past the end: any valid words will do
-      wq[qt] = (bb_cu64p)(uintptr_t)(a.drop_bits + ((size_t)(b * a.nh + h) * a.nq16 + q16) * a.nk64 * 16);
-    }
-  }
-  f32x4 oacc[QT][4];
-  float m_run[QT], nm[QT], l_run[QT];
-#pragma unroll
-  for (int qt = 0; qt < QT; ++qt) {
-    m_run[qt] = -INFINITY;     // running maximum (log2 domain) shared by the four lanes of a query
-    nm[qt] = 0.f;              // -(m_run), 0 while m_run is still -inf
-    l_run[qt] = 0.f;           // this lane's share of the row sum
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) oacc[qt][dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  }
-
-  // additive key mask of a tile in raw-score units (the C operand of Q K^T), one key per thread; -inf beyond Lk
-  auto mask_of = [&](int kv0) -> float {
-    const int key = kv0 + tid;
-    if (tid >= TK || key >= a.Lk) return -INFINITY;
-    return a.key_mask ? a.key_mask[(size_t)b * a.Lk + key] * inv_scale : 0.f;
-  };
-  uint4 kreg[CPT], vreg[CPT];
-  float mreg;
-  auto stage_load = [&](int kv0) {
-#pragma unroll
-    for (int i = 0; i < CPT; ++i) {
-      const int ch = tid + i * NT, row = ch >> 3, d0 = (ch & 7) * 8;
-      kreg[i] = vreg[i] = make_uint4(0, 0, 0, 0);                  // rows past the end are zero filled
-      if (ch < 512 && kv0 + row < a.Lk) {
-        kreg[i] = ld_frag_global(kp, a.ldk, kv0 + row, d0);
-        vreg[i] = ld_frag_global(vp, a.ldv, kv0 + row, d0);
-      }
-    }
-    mreg = mask_of(kv0);
-  };
-  auto stage_store = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < CPT; ++i) {
-      const int ch = tid + i * NT, row = ch >> 3, d0 = (ch & 7) * 8;
-      if (ch < 512) {
-        *reinterpret_cast<uint4*>(s_k[buf] + f2_off(row, ch & 7)) = kreg[i];
-        *reinterpret_cast<uint4*>(s_v[buf] + f2_off(row, ch & 7)) = vreg[i];
-      }
-    }
-    if (tid < TK) s_mask[buf][tid] = mreg;
-  };
-  stage_load(0);
-  stage_store(0);
-  if (TK < a.Lk) stage_load(TK);
-  __syncthreads();
-
-  // keep-bit words travel one (half, query tile) unit ahead of their use: every word is read once, so each scalar load is
-  // a cache miss with an L2 / HBM round trip to hide; 8 words per unit, 16 + 16 scalar registers
-  uint64_t kw[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) kw[i] = DROP ? wq[0][i] : 0;
-  for (int kv0 = 0, cur = 0; kv0 < a.Lk; kv0 += TK, cur ^= 1) {
-    const bf16_raw* ck = s_k[cur];
-    const bf16_raw* cv = s_v[cur];
-    const float* cmask = s_mask[cur];
-#pragma unroll
-    for (int hh = 0; hh < 2; ++hh) {       // halves of 32 keys: key tiles t = 2 hh, 2 hh + 1
-      // ---- S^T = K Q^T + mask
-      f32x4 sacc[QT][2];
-#pragma unroll
-      for (int tt = 0; tt < 2; ++tt) {
-        const int t = 2 * hh + tt;
-        const float4 mk = *reinterpret_cast<const float4*>(&cmask[t * 16 + g * 4]);
-#pragma unroll
-        for (int qt = 0; qt < QT; ++qt) sacc[qt][tt] = (f32x4){mk.x, mk.y, mk.z, mk.w};
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          const bf16x8 kf = f2_frag_rows(ck, t, ks, lane);
-#pragma unroll
-          for (int qt = 0; qt < QT; ++qt) sacc[qt][tt] = mfma16(kf, qf[qt][ks], sacc[qt][tt]);
-        }
-      }
-      // ---- first half: stage tile j+1 into the other buffer (its last readers passed the barrier that closed
-      //      iteration j-1) and start the global loads of tile j+2; both overlap the arithmetic below
-      if (hh == 0 && kv0 + TK < a.Lk) {
-        stage_store(cur ^ 1);
-        if (kv0 + 2 * TK < a.Lk) stage_load(kv0 + 2 * TK);
-      }
-      // ---- lazy running maximum (decision before this half's P exists)
-      float lm[QT];
-      bool grow = false;
-#pragma unroll
-      for (int qt = 0; qt < QT; ++qt) {
-        const f32x4 s0 = sacc[qt][0], s1 = sacc[qt][1];
-        lm[qt] = max3f(max3f(s0[0], s0[1], s0[2]), max3f(s0[3], s1[0], s1[1]), fmaxf(s1[2], s1[3])) * sc2;
-        grow |= lm[qt] > m_run[qt] + FWD2_THR;      // m_run = -inf: any finite score triggers the first update
-      }
-      if (__any(grow)) {
-#pragma unroll
-        for (int qt = 0; qt < QT; ++qt) {
-          const float m_new = fmaxf(m_run[qt], quad_max(lm[qt]));
-          const float nm_new = (m_new == -INFINITY) ? 0.f : -m_new;
-          const float alpha = fast_exp2(m_run[qt] + nm_new);  // exp2(m_old - m_new); first update: exp2(-inf) = 0, O = l = 0
-          m_run[qt] = m_new;
-          nm[qt] = nm_new;
-          l_run[qt] *= alpha;
-#pragma unroll
-          for (int dt = 0; dt < 4; ++dt) oacc[qt][dt] *= alpha;
-        }
-      }
-      // ---- P = exp2(s * sc2 - m); row sums before dropout; keep bits straight from scalar registers
-      bf16x8 pb[QT];
-#pragma unroll
-      for (int qt = 0; qt < QT; ++qt) {
-        uint64_t kwn[8];
-        if (DROP) {      // next unit: the other query tile of this half, or query tile 0 of the next half / key tile
-          const int kvn = (qt + 1 < QT || hh == 0) ? kv0 : (kv0 + TK < a.Lk ? kv0 + TK : kv0);
-          const int hn = qt + 1 < QT ? hh : hh ^ 1, qn = qt + 1 < QT ? qt + 1 : 0;
-#pragma unroll
-          for (int i = 0; i < 8; ++i) kwn[i] = wq[qn][(kvn >> 6) * 16 + hn * 8 + i];
-          __builtin_amdgcn_sched_barrier(0);      // the loads stay HERE, ahead of this unit's arithmetic
-        }
-        float psum = 0.f;
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            float p = fast_exp2(fmaf(sacc[qt][tt][r], sc2, nm[qt]));
-            psum += p;
-            if (DROP) p = drop_select(p, kw[tt * 4 + r]);
-            sacc[qt][tt][r] = p;
-          }
-        l_run[qt] += psum;
-        pb[qt] = pack_pair(sacc[qt][0], sacc[qt][1]);
-        if (DROP) {
-#pragma unroll
-          for (int i = 0; i < 8; ++i) kw[i] = kwn[i];
-        }
-      }
-      // ---- O^T += V^T P^T over this half's 32 keys: k-slot (g, j) <-> key 32 hh + 16 (j >> 2) + 4 g + (j & 3)
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        const bf16x8 vf = f2_frag_tr(cv, 32 * hh + 4 * g, 32 * hh + 16 + 4 * g, dt * 16, lane);
-#pragma unroll
-        for (int qt = 0; qt < QT; ++qt) oacc[qt][dt] = mfma16(vf, pb[qt], oacc[qt][dt]);
-      }
-
-    }
-    __syncthreads();  // one barrier per tile: buffer `cur` is free again, buffer `cur^1` is complete
-  }
-
-  // ---- epilogue: normalise (dropout scaling folded in), store O[q][h*64 + dt*16 + g*4 .. +3] and the log-sum-exp
-  const float ks = DROP ? a.keep_scale : 1.0f;
-#pragma unroll
-  for (int qt = 0; qt < QT; ++qt) {
-    const float l = quad_sum(l_run[qt]);
-    const float inv = ks / l;
-    if (qrow[qt] < a.Lq) {
-      bf16_raw* op = (bf16_raw*)a.o + (size_t)b * a.bso + (size_t)qrow[qt] * a.ldo + h * ATTN_D;
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt)
-        st4<bf16_raw>(op + dt * 16 + g * 4, make_float4(oacc[qt][dt][0] * inv, oacc[qt][dt][1] * inv,
-                                                         oacc[qt][dt][2] * inv, oacc[qt][dt][3] * inv));
-      if (a.lse && g == 0) a.lse[((size_t)b * a.nh + h) * a.Lq + qrow[qt]] = (log2f(l) - nm[qt]) * LN2;
-    }
-  }
-}
-
-// Round 5: the same kernel on a further diet (see the comments inside): fused multiply-add before the maximum, select
-// before the packed conversion, keep-bit words of a whole tile requested in front of the tile barrier.
-// ABL (diagnostics, BEVBERT_FWD_ABL; results WRONG): 1 = no softmax arithmetic, 2 = no P V products, 4 = no Q K^T products,
-// 8 = no K / V staging after tile 1, 16 = no running-maximum check, 64 = one key tile only
-template <int NW, bool DROP, int ABL = 0>
-__global__ __launch_bounds__(64 * NW, 4) void attn_fwd3_kernel(AttnArgs a) {
-  constexpr int QT = 2;                      // 16-query tiles per wave
-  constexpr int NT = 64 * NW;
-  constexpr int CPT = (512 + NT - 1) / NT;   // 16-byte chunks of a [64][64] bf16 tile per thread
+  constexpr int CPT = (512 + NT - 1) / NT;   // 16-byte chunks of a [64][64] bf16 tile per thread.  NT = 256 divides 512, so
+  // the ``ch < 512`` tests below never fail; the compiler cannot see that and the kernel's code changes without them
+  // (1 208 instead of 1 313 instructions with dropout), so they stay until a change that measures the difference
   __shared__ __attribute__((aligned(16))) bf16_raw s_k[2][F2_TILE];
   __shared__ __attribute__((aligned(16))) bf16_raw s_v[2][F2_TILE];
   __shared__ __attribute__((aligned(16))) float s_mask[2][TK];
@@ -345,8 +140,7 @@ __global__ __launch_bounds__(64 * NW, 4) void attn_fwd3_kernel(AttnArgs a) {
   for (int qt = 0; qt < QT; ++qt)
 #pragma unroll
     for (int i = 0; i < 16; ++i) kw[qt][i] = DROP ? wq[qt][i] : 0;
-  const int Lk_run = (ABL & 64) ? (a.Lk < TK ? a.Lk : TK) : a.Lk;
-  for (int kv0 = 0, cur = 0; kv0 < Lk_run; kv0 += TK, cur ^= 1) {
+  for (int kv0 = 0, cur = 0; kv0 < a.Lk; kv0 += TK, cur ^= 1) {
     const bf16_raw* ck = s_k[cur];
     const bf16_raw* cv = s_v[cur];
     const float* cmask = s_mask[cur];
@@ -364,12 +158,12 @@ __global__ __launch_bounds__(64 * NW, 4) void attn_fwd3_kernel(AttnArgs a) {
         for (int ks = 0; ks < 2; ++ks) {
           const bf16x8 kf = f2_frag_rows(ck, t, ks, lane);
 #pragma unroll
-          for (int qt = 0; qt < QT; ++qt) if (!(ABL & 4)) sacc[qt][tt] = mfma16(kf, qf[qt][ks], sacc[qt][tt]);
+          for (int qt = 0; qt < QT; ++qt) sacc[qt][tt] = mfma16(kf, qf[qt][ks], sacc[qt][tt]);
         }
       }
       // ---- first half: stage tile j+1 into the other buffer (its last readers passed the barrier that closed
       //      iteration j-1) and start the global loads of tile j+2; both overlap the arithmetic below
-      if (hh == 0 && kv0 + TK < a.Lk && !((ABL & 8) && kv0 > 0)) {
+      if (hh == 0 && kv0 + TK < a.Lk) {
         stage_store(cur ^ 1);
         if (kv0 + 2 * TK < a.Lk) stage_load(kv0 + 2 * TK);
       }
@@ -390,7 +184,7 @@ __global__ __launch_bounds__(64 * NW, 4) void attn_fwd3_kernel(AttnArgs a) {
         lm[qt] = max3f(max3f(s0[0], s0[1], s0[2]), max3f(s0[3], s1[0], s1[1]), fmaxf(s1[2], s1[3]));
         grow |= (lm[qt] > FWD2_THR) | ((m_run[qt] == -INFINITY) & (lm[qt] > -INFINITY));   // no maximum yet: any finite score sets it
       }
-      if ((ABL & 16) ? (kv0 == 0 && hh == 0) : __any(grow)) {
+      if (__any(grow)) {
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) {
           const float m_new = fmaxf(m_run[qt], quad_max(lm[qt]) - nm[qt]);      // lm is relative to the stale maximum
@@ -419,10 +213,10 @@ __global__ __launch_bounds__(64 * NW, 4) void attn_fwd3_kernel(AttnArgs a) {
         for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            float p = (ABL & 1) ? sacc[qt][tt][r] : fast_exp2(sacc[qt][tt][r]);
+            float p = fast_exp2(sacc[qt][tt][r]);
             psum += p;
-            if (DROP && !(ABL & 1)) {
-              p = drop_select(p, kw[qt][(2 * hh + tt) * 4 + r]);
+            if (DROP) {
+              p = keep_select(p, kw[qt][(2 * hh + tt) * 4 + r]);
               asm("" : "+v"(p));
             }
             sacc[qt][tt][r] = p;
@@ -435,7 +229,7 @@ __global__ __launch_bounds__(64 * NW, 4) void attn_fwd3_kernel(AttnArgs a) {
       for (int dt = 0; dt < 4; ++dt) {
         const bf16x8 vf = f2_frag_tr(cv, 32 * hh + 4 * g, 32 * hh + 16 + 4 * g, dt * 16, lane);
 #pragma unroll
-        for (int qt = 0; qt < QT; ++qt) if (!(ABL & 2)) oacc[qt][dt] = mfma16(vf, pb[qt], oacc[qt][dt]);
+        for (int qt = 0; qt < QT; ++qt) oacc[qt][dt] = mfma16(vf, pb[qt], oacc[qt][dt]);
       }
 
     }
@@ -590,52 +384,17 @@ int attn_drop_bits(const AttnArgs& a, uint64_t* bits_f, uint64_t* bits_b, uint32
 // =============================================================================================
 // launcher
 // =============================================================================================
-template <int NW>
-static int launch_fwd2(const AttnArgs& a_in, hipStream_t st) {
-  AttnArgs a = a_in;
-  a.nblk = (a.Lq + 32 * NW - 1) / (32 * NW);
-  const dim3 grid((unsigned)a.nblk * a.nh * a.B);
-  // BEVBERT_FWD_VAR=0: the round-3 kernel (A/B measurements, on-GPU cross-check)
-  static const int var = [] { const char* v = getenv("BEVBERT_FWD_VAR"); return v ? atoi(v) : 1; }();
-  if (var == 0) {
-    if (a.drop_p > 0.f) hipLaunchKernelGGL((attn_fwd2_kernel<NW, true>), grid, dim3(64 * NW), 0, st, a);
-    else hipLaunchKernelGGL((attn_fwd2_kernel<NW, false>), grid, dim3(64 * NW), 0, st, a);
-  } else {
-    static const int abl = [] { const char* v = getenv("BEVBERT_FWD_ABL"); return v ? atoi(v) : 0; }();
-    if (abl && a.drop_p > 0.f && NW == 4) {
-      switch (abl) {
-        case 1: hipLaunchKernelGGL((attn_fwd3_kernel<4, true, 1>), grid, dim3(256), 0, st, a); return BB_OK;
-        case 2: hipLaunchKernelGGL((attn_fwd3_kernel<4, true, 2>), grid, dim3(256), 0, st, a); return BB_OK;
-        case 4: hipLaunchKernelGGL((attn_fwd3_kernel<4, true, 4>), grid, dim3(256), 0, st, a); return BB_OK;
-        case 6: hipLaunchKernelGGL((attn_fwd3_kernel<4, true, 6>), grid, dim3(256), 0, st, a); return BB_OK;
-        case 7: hipLaunchKernelGGL((attn_fwd3_kernel<4, true, 7>), grid, dim3(256), 0, st, a); return BB_OK;
-        case 8: hipLaunchKernelGGL((attn_fwd3_kernel<4, true, 8>), grid, dim3(256), 0, st, a); return BB_OK;
-        case 16: hipLaunchKernelGGL((attn_fwd3_kernel<4, true, 16>), grid, dim3(256), 0, st, a); return BB_OK;
-        case 17: hipLaunchKernelGGL((attn_fwd3_kernel<4, true, 17>), grid, dim3(256), 0, st, a); return BB_OK;
-        case 31: hipLaunchKernelGGL((attn_fwd3_kernel<4, true, 31>), grid, dim3(256), 0, st, a); return BB_OK;
-        case 64: hipLaunchKernelGGL((attn_fwd3_kernel<4, true, 64>), grid, dim3(256), 0, st, a); return BB_OK;
-        case 95: hipLaunchKernelGGL((attn_fwd3_kernel<4, true, 95>), grid, dim3(256), 0, st, a); return BB_OK;
-        default: break;
-      }
-    }
-    if (a.drop_p > 0.f) hipLaunchKernelGGL((attn_fwd3_kernel<NW, true>), grid, dim3(64 * NW), 0, st, a);
-    else hipLaunchKernelGGL((attn_fwd3_kernel<NW, false>), grid, dim3(64 * NW), 0, st, a);
-  }
-  BB_CHECK_LAUNCH("attn_fwd(mfma, gen 2)");
-  return BB_OK;
-}
-
 // The second-generation forward covers everything without a per-element additive bias (the graph bias of the global
 // map encoder: a few dozen nodes, stays on attn_mfma_fwd_kernel) and, with dropout, needs the keep-bit matrix.
 bool attn_fwd2_supported(const AttnArgs& a) { return a.bias == nullptr && (a.drop_p <= 0.f || a.drop_bits != nullptr); }
 
-int attn_fwd2(const AttnArgs& a, hipStream_t st) {
-  BB_REQUIRE(attn_mfma_operands_aligned(a, false), "attention (MFMA path): " ATTN_MFMA_ALIGN_MSG);
-  // BEVBERT_FWD2_NW in {4, 7}: force a workgroup shape (A/B measurements)
-  static const int force = [] { const char* v = getenv("BEVBERT_FWD2_NW"); return v ? atoi(v) : 0; }();
-  // 4 waves x 32 queries: four workgroups share a CU (16 waves).  The 7-wave shape (two workgroups of 224 queries cover
-  // the 441 BEV cells without the 14 % padding of 128-query blocks) measured slower: 97 vs 88 us (BEVBERT_FWD2_NW=7)
-  if (force == 7) return launch_fwd2<7>(a, st);
-  if (force == 8) return launch_fwd2<8>(a, st);
-  return launch_fwd2<4>(a, st);
+int attn_fwd2(const AttnArgs& a_in, hipStream_t st) {
+  BB_REQUIRE(attn_mfma_operands_aligned(a_in, false), "attention (MFMA path): " ATTN_MFMA_ALIGN_MSG);
+  AttnArgs a = a_in;
+  a.nblk = (a.Lq + 32 * F2_NW - 1) / (32 * F2_NW);
+  const dim3 grid((unsigned)a.nblk * a.nh * a.B);
+  if (a.drop_p > 0.f) hipLaunchKernelGGL((attn_fwd3_kernel<true>), grid, dim3(64 * F2_NW), 0, st, a);
+  else hipLaunchKernelGGL((attn_fwd3_kernel<false>), grid, dim3(64 * F2_NW), 0, st, a);
+  BB_CHECK_LAUNCH("attn_fwd(mfma, gen 2)");
+  return BB_OK;
 }

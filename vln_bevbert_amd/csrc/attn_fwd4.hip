@@ -11,7 +11,8 @@
 //     what a kernel can win beyond that is everything that is NOT arithmetic.  This file is compiled without the SLP vectoriser
 //     and keeps its row sums in scalar chains so that no packed fp32 instruction sits in the loop (measured: no difference,
 //     77.6 against 77.7 us -- they were not what keeps the loop from the probe's overlap);
-//   * the s_memtime timeline of one workgroup of the non-persistent version (BEVBERT_FWD4_ABL=32): 22 % of a workgroup's life
+//   * the s_memtime timeline of one workgroup of the non-persistent version
+//     (profiles/r05_attention_fwd4_workgroup_timeline.txt): 22 % of a workgroup's life
 //     was its prologue -- 256 workgroups start a round together and ask for their first 110 KB at once, 28 MB at HBM speed --
 //     and the units in which a wave fetched fragments from LDS took twice the time of the others.
 // Hence:
@@ -32,9 +33,6 @@
 //     would wait for them), and 64 wave masks per key tile would not fit the scalar registers.  Element e = 8 qt + 4 tt + r of
 //     the lane sits at bit e >> 1 of half (e & 1): the mask of a packed bf16 pair is two packed 16-bit shifts of the
 //     word, the drop one AND on the pair.
-//
-// ABL (diagnostics, BEVBERT_FWD4_ABL; results WRONG): 1 = no softmax arithmetic, 2 = no P V products, 4 = no Q K^T products;
-// 32 = s_memtime stamps of one workgroup's second item -> $BEVBERT_FWD4_DBG (results correct)
 #include <type_traits>
 
 #include "attn_mfma_common.h"
@@ -51,11 +49,8 @@ struct F4Lds {
   static constexpr int bytes = mask_off + 2 * F4_NK * 4;
 };
 
-__device__ __forceinline__ float f4_max3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
-
-template <bool DROP, int ABL>
-__global__ __launch_bounds__(512, 2) void attn_fwd4_kernel(AttnArgs a, const uint32_t* __restrict__ bits_l, int nitems,
-                                                           unsigned long long* dbg) {
+template <bool DROP>
+__global__ __launch_bounds__(512, 2) void attn_fwd4_kernel(AttnArgs a, const uint32_t* __restrict__ bits_l, int nitems) {
   extern __shared__ __attribute__((aligned(16))) unsigned char f4_smem[];
   bf16_raw* s_k = reinterpret_cast<bf16_raw*>(f4_smem + F4Lds::k_off);
   bf16_raw* s_v = reinterpret_cast<bf16_raw*>(f4_smem + F4Lds::v_off);
@@ -70,10 +65,6 @@ __global__ __launch_bounds__(512, 2) void attn_fwd4_kernel(AttnArgs a, const uin
     const int t = item / a.nblk;
     h = t % a.nh;
     b = t / a.nh;
-  };
-  bool dbg_on = false;
-  auto stamp = [&](int slot) {
-    if ((ABL & 32) && dbg_on && lane == 0) dbg[w * 64 + slot] = __builtin_amdgcn_s_memtime();
   };
 
   if (w == 7) {
@@ -211,17 +202,15 @@ __global__ __launch_bounds__(512, 2) void attn_fwd4_kernel(AttnArgs a, const uin
     for (int tt = 0; tt < 2; ++tt) {
       dst[tt] = (f32x4){mk[tt].x, mk[tt].y, mk[tt].z, mk[tt].w};
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) if (!(ABL & 4)) dst[tt] = mfma16(kf[tt][ks], q[ks], dst[tt]);
+      for (int ks = 0; ks < 2; ++ks) dst[tt] = mfma16(kf[tt][ks], q[ks], dst[tt]);
     }
   };
   auto issue_PV = [&](f32x4 (&o)[4], const bf16x8& pb) {
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt) if (!(ABL & 2)) o[dt] = mfma16(vf[dt], pb, o[dt]);
+    for (int dt = 0; dt < 4; ++dt) o[dt] = mfma16(vf[dt], pb, o[dt]);
   };
 
   for (int it = 0; it < my_items; ++it) {
-    dbg_on = (ABL & 32) && blockIdx.x == 100 && it == 1;
-    stamp(0);
     const int h = hb_h, b = hb_b;                      // qf / qrow / wl belong to this item; they move on in the last iteration
     int orow[4];
 #pragma unroll
@@ -238,7 +227,6 @@ __global__ __launch_bounds__(512, 2) void attn_fwd4_kernel(AttnArgs a, const uin
     cmask = s_mask + (it & 1) * F4_NK;
     __builtin_amdgcn_s_barrier();                      // tile 0 and the mask row of this item are in LDS
     asm volatile("" : : : "memory");
-    stamp(1);
     load_k(0);
     load_v(0);
     issue_S(sa[0], qf[0]);
@@ -261,7 +249,6 @@ __global__ __launch_bounds__(512, 2) void attn_fwd4_kernel(AttnArgs a, const uin
 #pragma unroll
       for (int qt = 0; qt < 4; ++qt) {
         const int N = (qt & 1) ^ 1, P = qt & 1;
-        stamp(2 + 4 * s + qt);
         // tile (s + 1) / 2 must have landed before the K fragments of iteration s + 1 are fetched (end of this unit)
         if (qt == 1 && (s & 1) && !LAST) {
           __builtin_amdgcn_s_barrier();
@@ -273,7 +260,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd4_kernel(AttnArgs a, const uin
 #pragma unroll
           for (int r = 0; r < 4; ++r) sa[qt][tt][r] = fmaf(sa[qt][tt][r], sc2, nm[qt]);
         const f32x4 s0 = sa[qt][0], s1 = sa[qt][1];
-        const float lm = f4_max3(f4_max3(s0[0], s0[1], s0[2]), f4_max3(s0[3], s1[0], s1[1]), fmaxf(s1[2], s1[3]));
+        const float lm = max3f(max3f(s0[0], s0[1], s0[2]), max3f(s0[3], s1[0], s1[1]), fmaxf(s1[2], s1[3]));
         if (__any(lm > thr[qt])) {
           const float m_new = fmaxf(m_run[qt], quad_max(lm) - nm[qt]);          // lm is relative to the stale maximum
           const float nm_new = (m_new == -INFINITY) ? 0.f : -m_new;
@@ -297,12 +284,12 @@ __global__ __launch_bounds__(512, 2) void attn_fwd4_kernel(AttnArgs a, const uin
         uint32_t pk[4];
         auto soft_pair = [&](int i) {
           const int tt = i >> 1, r0 = 2 * (i & 1);
-          const float p0 = (ABL & 1) ? sa[qt][tt][r0] : fast_exp2(sa[qt][tt][r0]);
-          const float p1 = (ABL & 1) ? sa[qt][tt][r0 + 1] : fast_exp2(sa[qt][tt][r0 + 1]);
+          const float p0 = fast_exp2(sa[qt][tt][r0]);
+          const float p1 = fast_exp2(sa[qt][tt][r0 + 1]);
           ps0 += p0;
           ps1 += p1;
           pk[i] = pack_bf16x2(p0, p1);
-          if (DROP && !(ABL & 1)) {
+          if (DROP) {
             typedef short s16x2 __attribute__((ext_vector_type(2)));
             const s16x2 wv = __builtin_bit_cast(s16x2, wd0);
             const s16x2 m = (s16x2)(wv << (short)(15 - 4 * qt - i)) >> (short)15;
@@ -338,7 +325,6 @@ __global__ __launch_bounds__(512, 2) void attn_fwd4_kernel(AttnArgs a, const uin
     for (int s = 0; s < nsteps - 1; ++s) iteration(s, std::false_type{});
     iteration(nsteps - 1, std::true_type{});
     issue_PV(oacc[3], pbq[1]);
-    stamp(60);
 
     // ---- epilogue: normalise (dropout scaling folded in) and store O as whole 128-byte rows, 16 bytes per lane, through an
     //      LDS region nobody reads any more (the accumulator layout would give sixteen 32-byte pieces per store instruction).
@@ -371,7 +357,6 @@ __global__ __launch_bounds__(512, 2) void attn_fwd4_kernel(AttnArgs a, const uin
         if (q0 + row < a.Lq) *reinterpret_cast<uint4*>(op + (size_t)(q0 + row) * a.ldo + ch * 8) = val;
       }
     }
-    stamp(62);
   }
 }
 
@@ -389,9 +374,9 @@ int attn_fwd4_workgroups() {   // also the CU count of the occupancy rule (AttnK
   return (v && atoi(v) > 0) ? atoi(v) : ncu;
 }
 
-template <bool D_, int A_ = 0>
+template <bool D_>
 static int launch_fwd4(const AttnArgs& a_in, const uint32_t* bits_l, hipStream_t st) {
-  static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd4_kernel<D_, A_>),
+  static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd4_kernel<D_>),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, F4Lds::bytes) == hipSuccess;
   BB_REQUIRE(ok, "attention fwd (gen 4): cannot raise the dynamic LDS limit to %d bytes", F4Lds::bytes);
   // one workgroup per CU (its LDS fills the CU), each walking items blockIdx.x, blockIdx.x + gridDim.x, ...
@@ -400,27 +385,8 @@ static int launch_fwd4(const AttnArgs& a_in, const uint32_t* bits_l, hipStream_t
   a.nblk = (a.Lq + F4_NQ - 1) / F4_NQ;
   const int nitems = a.nblk * a.nh * a.B;
   const int grid = nitems < ncu ? nitems : ncu;
-  unsigned long long* dbg = nullptr;
-  if (A_ & 32) {                                       // diagnostics: stamps of one workgroup -> $BEVBERT_FWD4_DBG (text)
-    static unsigned long long* buf = [] { void* p = nullptr; (void)hipMalloc(&p, 8 * 64 * 8); return (unsigned long long*)p; }();
-    dbg = buf;
-    (void)hipMemsetAsync(dbg, 0, 8 * 64 * 8, st);
-  }
-  hipLaunchKernelGGL((attn_fwd4_kernel<D_, A_>), dim3((unsigned)grid), dim3(512), F4Lds::bytes, st, a, bits_l, nitems, dbg);
+  hipLaunchKernelGGL((attn_fwd4_kernel<D_>), dim3((unsigned)grid), dim3(512), F4Lds::bytes, st, a, bits_l, nitems);
   BB_CHECK_LAUNCH("attn_fwd(mfma, gen 4)");
-  if (A_ & 32) {
-    unsigned long long host[8 * 64];
-    (void)hipStreamSynchronize(st);
-    (void)hipMemcpy(host, dbg, sizeof(host), hipMemcpyDeviceToHost);
-    const char* path = getenv("BEVBERT_FWD4_DBG");
-    if (FILE* f = fopen(path ? path : "/tmp/fwd4_dbg.txt", "w")) {
-      for (int w = 0; w < 8; ++w) {
-        for (int i = 0; i < 64; ++i) fprintf(f, "%llu ", host[w * 64 + i] ? host[w * 64 + i] - host[0] : 0ull);
-        fprintf(f, "\n");
-      }
-      fclose(f);
-    }
-  }
   return BB_OK;
 }
 
@@ -439,18 +405,6 @@ bool attn_fwd4_supported(const AttnArgs& a, int ncu, bool forced) {
 
 int attn_fwd4(const AttnArgs& a, const uint32_t* bits_l, hipStream_t st) {
   BB_REQUIRE(attn_mfma_operands_aligned(a, false), "attention (MFMA path): " ATTN_MFMA_ALIGN_MSG);
-  static const int abl = [] { const char* v = getenv("BEVBERT_FWD4_ABL"); return v ? atoi(v) : 0; }();
-  if (abl && a.drop_p > 0.f) {
-    switch (abl) {
-      case 1: return launch_fwd4<true, 1>(a, bits_l, st);
-      case 2: return launch_fwd4<true, 2>(a, bits_l, st);
-      case 4: return launch_fwd4<true, 4>(a, bits_l, st);
-      case 6: return launch_fwd4<true, 6>(a, bits_l, st);
-      case 7: return launch_fwd4<true, 7>(a, bits_l, st);
-      case 32: return launch_fwd4<true, 32>(a, bits_l, st);
-      default: break;
-    }
-  }
   if (a.drop_p > 0.f) return launch_fwd4<true>(a, bits_l, st);
   return launch_fwd4<false>(a, bits_l, st);
 }

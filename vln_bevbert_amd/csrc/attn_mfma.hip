@@ -555,12 +555,6 @@ __global__ __launch_bounds__(256, KT == 1 ? 2 : 1) void attn_mfma_dkv_kernel(Att
 // =============================================================================================
 // launchers
 // =============================================================================================
-// Tile-shape knobs for A/B measurements (read once): BEVBERT_FWD_QT / BEVBERT_DQ_QT / BEVBERT_DKV_KT in {1, 2}.
-static int env_knob(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return (v && (v[0] == '1' || v[0] == '2')) ? v[0] - '0' : dflt;
-}
-
 // compile-time specialisation on (graph bias present, dropout active): the common launches carry neither
 #define BB_DISPATCH_FLAGS(KERNEL, N, NBLK, SMEM)                                                         \
   do {                                                                                                  \
@@ -576,9 +570,8 @@ static int env_knob(const char* name, int dflt) {
 
 int attn_mfma_fwd(const AttnArgs& a_in, hipStream_t st) {
   const AttnArgs& a = a_in;
-  static const int fwd_qt = env_knob("BEVBERT_FWD_QT", 2);
   BB_REQUIRE(attn_mfma_operands_aligned(a, false), "attention (MFMA path): " ATTN_MFMA_ALIGN_MSG);
-  if (a.Lq > 64 && fwd_qt == 2)
+  if (a.Lq > 64)
     BB_DISPATCH_FLAGS(attn_mfma_fwd_kernel, 2, (a.Lq + 127) / 128, 0);
   else
     BB_DISPATCH_FLAGS(attn_mfma_fwd_kernel, 1, (a.Lq + 63) / 64, 0);
@@ -597,8 +590,7 @@ int attn_mfma_bwd(const AttnArgs& a_in, hipStream_t st) {
   BB_REQUIRE(attn_mfma_operands_aligned(a, false), "attention (MFMA path): " ATTN_MFMA_ALIGN_MSG);
   BB_REQUIRE(((uintptr_t)a.dout % 16) == 0 && ((uintptr_t)a.dq % 16) == 0 && ((uintptr_t)a.dk % 16) == 0 &&
                  ((uintptr_t)a.dv % 16) == 0, "attention bwd (MFMA path): gradient pointers must be 16-byte aligned");
-  static const int dq_qt = env_knob("BEVBERT_DQ_QT", 2), dkv_kt = env_knob("BEVBERT_DKV_KT", 1);
-  if (a.Lq > 64 && dq_qt == 2)
+  if (a.Lq > 64)
     BB_DISPATCH_FLAGS(attn_mfma_dq_kernel, 2, (a.Lq + 127) / 128, 0);
   else
     BB_DISPATCH_FLAGS(attn_mfma_dq_kernel, 1, (a.Lq + 63) / 64, 0);
@@ -606,15 +598,11 @@ int attn_mfma_bwd(const AttnArgs& a_in, hipStream_t st) {
     bool ok = true;
     ok &= raise_lds_limit<1, false, false>() && raise_lds_limit<1, false, true>();
     ok &= raise_lds_limit<1, true, false>() && raise_lds_limit<1, true, true>();
-    ok &= raise_lds_limit<2, false, false>() && raise_lds_limit<2, false, true>();
-    ok &= raise_lds_limit<2, true, false>() && raise_lds_limit<2, true, true>();
     return ok;
   }();
   BB_REQUIRE(attr_ok, "attention bwd: cannot raise the dynamic LDS limit to %d bytes", DKV_SMEM_BYTES);
-  if (a.Lk > 64 && dkv_kt == 2)
-    BB_DISPATCH_FLAGS(attn_mfma_dkv_kernel, 2, (a.Lk + 127) / 128, DKV_SMEM_BYTES);
-  else
-    BB_DISPATCH_FLAGS(attn_mfma_dkv_kernel, 1, (a.Lk + 63) / 64, DKV_SMEM_BYTES);
+  // one key tile per wave; KT = 2 (128 keys per workgroup) was slower: profiles/r01b_attn_microbench_dkv_kt2.jsonl
+  BB_DISPATCH_FLAGS(attn_mfma_dkv_kernel, 1, (a.Lk + 63) / 64, DKV_SMEM_BYTES);
   BB_CHECK_LAUNCH("attn_bwd(mfma)");
   return BB_OK;
 }

@@ -1,5 +1,5 @@
-// Building blocks shared by the MFMA attention kernels (attn_mfma.hip: forward + two-kernel backward;
-// attn_bwd1.hip: single-pass backward): fragment loads, tile staging, the hardware-transposing LDS read.
+// Building blocks shared by every MFMA attention kernel: fragment loads, tile staging, lane reductions, the keep-bit
+// select, the hardware-transposing LDS read.
 #pragma once
 #include <stdlib.h>
 
@@ -83,6 +83,29 @@ __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_ex
 __device__ __forceinline__ bf16x8 pack_pair(const f32x4& a, const f32x4& b) {
   return as_bf16x8(make_uint4(pack_bf16x2(a[0], a[1]), pack_bf16x2(a[2], a[3]), pack_bf16x2(b[0], b[1]),
                               pack_bf16x2(b[2], b[3])));
+}
+__device__ __forceinline__ uint2 pack4(const f32x4& v) {
+  return make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
+}
+__device__ __forceinline__ bf16x8 join_pair(uint2 a, uint2 b) { return as_bf16x8(make_uint4(a.x, a.y, b.x, b.y)); }
+__device__ __forceinline__ float max3f(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
+
+// Keep bits as 64-bit lane masks: fetched by uniform loads through the scalar cache (constant address space), applied as
+// keep ? p : 0 with ONE v_cndmask_b32 on an SGPR-pair condition (the compiler sees the instruction, so the
+// transcendental-result hazard behind v_exp_f32 is padded by it, unlike inside inline asm)
+typedef const __attribute__((address_space(4))) uint64_t* bb_cu64p;
+__device__ __forceinline__ float keep_select(float p, uint64_t lane_mask) {
+  return __builtin_amdgcn_inverse_ballot_w64(lane_mask) ? p : 0.f;
+}
+
+// sum over the 8 lanes that share a tile row (lanes 8 j .. 8 j + 7) on the DPP network: no LDS round trip
+template <int CTRL> __device__ __forceinline__ float dpp_f32(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
+}
+__device__ __forceinline__ float sum8(float v) {
+  v += dpp_f32<0xB1>(v);      // quad_perm [1,0,3,2]
+  v += dpp_f32<0x4E>(v);      // quad_perm [2,3,0,1]
+  return v + dpp_f32<0x141>(v);   // row_half_mirror: lane i <-> 7 - i of its half row
 }
 // reduce over the four lanes that own the same query/key column (l&15)
 __device__ __forceinline__ float quad_max(float v) {

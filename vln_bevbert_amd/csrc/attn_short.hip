@@ -24,29 +24,12 @@
 // Dropout: same element numbering, hash and keep-word layout as every other attention kernel (attn_common.h).
 #include "attn_mfma_common.h"
 
-typedef const __attribute__((address_space(4))) uint64_t* sh_cu64p;   // uniform loads through the scalar cache
-
-template <int CTRL> __device__ __forceinline__ float sh_dpp(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float sh_sum8(float v) {   // sum over the 8 lanes that hold one 64-element row
-  v += sh_dpp<0xB1>(v);           // quad_perm [1,0,3,2]
-  v += sh_dpp<0x4E>(v);           // quad_perm [2,3,0,1]
-  return v + sh_dpp<0x141>(v);    // row_half_mirror
-}
-__device__ __forceinline__ bf16x8 sh_join(uint2 a, uint2 b) { return as_bf16x8(make_uint4(a.x, a.y, b.x, b.y)); }
-__device__ __forceinline__ uint2 sh_pack4(const f32x4& v) {
-  return make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
-}
-// Transposing fragment read whose second group of four k-slot rows may lie beyond the image (odd tile counts): zeros.
-template <bool HI>
-__device__ __forceinline__ bf16x8 sh_frag_tr(const bf16_raw* img, int stride, int row_lo, int row_hi, int col0, int lane) {
+// lds_frag_tr whose second group of four k-slot rows lies beyond the image (the last half of an odd tile count): zeros.
+__device__ __forceinline__ bf16x8 sh_frag_tr_lo(const bf16_raw* img, int stride, int row_lo, int col0, int lane) {
   const int i = lane & 15;
   const int off = (i >> 2) * stride + col0 + 4 * (i & 3);
   const uint2 lo = lds_tr16(img + row_lo * stride + off);
-  uint2 hi = make_uint2(0u, 0u);
-  if (HI) hi = lds_tr16(img + row_hi * stride + off);
-  return as_bf16x8(make_uint4(lo.x, lo.y, hi.x, hi.y));
+  return as_bf16x8(make_uint4(lo.x, lo.y, 0u, 0u));
 }
 
 // A wave's 16 x 64 result tile leaves through LDS as WHOLE 128-byte rows: the accumulators hold, per lane, four consecutive
@@ -146,8 +129,8 @@ __global__ __launch_bounds__(512) void attn_short_fwd_kernel(AttnArgs a) {
   const float m2 = (mx == -INFINITY) ? 0.f : mx * sc2;
   float psum = 0.f;
   const uint32_t rbase = attn_row_base(a, b, h, qrow);
-  sh_cu64p wq = nullptr;
-  if (DROP == 2) wq = (sh_cu64p)(uintptr_t)(a.drop_bits + attn_bits_word(a, bh, qt, 0, 0, 0));
+  bb_cu64p wq = nullptr;
+  if (DROP == 2) wq = (bb_cu64p)(uintptr_t)(a.drop_bits + attn_bits_word(a, bh, qt, 0, 0, 0));
 #pragma unroll
   for (int t = 0; t < NKT; ++t) {
     float p[4];
@@ -195,12 +178,12 @@ __global__ __launch_bounds__(512) void attn_short_fwd_kernel(AttnArgs a) {
       const bf16x8 pb = pack_pair(s[2 * m], s[(2 * m + 1 < NKT) ? 2 * m + 1 : 0]);
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt)
-        o[dt] = mfma16(sh_frag_tr<true>(s_v, LDT, 32 * m + 4 * g, 32 * m + 16 + 4 * g, dt * 16, lane), pb, o[dt]);
+        o[dt] = mfma16(lds_frag_tr(s_v, LDT, 32 * m + 4 * g, 32 * m + 16 + 4 * g, dt * 16, lane), pb, o[dt]);
     } else {
       const bf16x8 pb = pack_pair(s[2 * m], zero);
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt)
-        o[dt] = mfma16(sh_frag_tr<false>(s_v, LDT, 32 * m + 4 * g, 0, dt * 16, lane), pb, o[dt]);
+        o[dt] = mfma16(sh_frag_tr_lo(s_v, LDT, 32 * m + 4 * g, dt * 16, lane), pb, o[dt]);
     }
   }
   const float l = quad_sum(psum);
@@ -283,7 +266,7 @@ __global__ __launch_bounds__(384) void attn_short_bwd_kernel(AttnArgs a) {
       if (row < a.Lq) {
         qv[i] = ld_frag_global(qp, a.ldq, row, ch * 8);
         dv[i] = ld_frag_global(dop, a.ldo, row, ch * 8);
-        if (!(a.dbg & 2)) ov[i] = ld_frag_global(op, a.ldo, row, ch * 8);
+        ov[i] = ld_frag_global(op, a.ldo, row, ch * 8);
       }
     }
 #pragma unroll
@@ -299,7 +282,7 @@ __global__ __launch_bounds__(384) void attn_short_bwd_kernel(AttnArgs a) {
         for (int j = 0; j < 4; ++j)
           dsum += __uint_as_float(dw[j] << 16) * __uint_as_float(ow[j] << 16) +
                   __uint_as_float(dw[j] & 0xffff0000u) * __uint_as_float(ow[j] & 0xffff0000u);
-        dsum = sh_sum8(dsum);
+        dsum = sum8(dsum);
         if ((lane & 7) == 0) s_dlt[row] = dsum;
       }
     }
@@ -346,23 +329,23 @@ __global__ __launch_bounds__(384) void attn_short_bwd_kernel(AttnArgs a) {
             const float dpd = keep ? dp[r] * ks : 0.f;
             dsv[r] = p * (dpd - drow[r]);
           }
-          pp[j] = sh_pack4(pd);
-          pds[j] = sh_pack4(dsv);
+          pp[j] = pack4(pd);
+          pds[j] = pack4(dsv);
           *reinterpret_cast<uint2*>(s_ds + (16 * t + c) * DS_LD + 16 * qt + 4 * g) = pds[j];
         }
       }
-      const bf16x8 pb = sh_join(pp[0], pp[1]), dsb = sh_join(pds[0], pds[1]);
+      const bf16x8 pb = join_pair(pp[0], pp[1]), dsb = join_pair(pds[0], pds[1]);
       if (2 * m + 1 < NQT) {
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
-          dv[dt] = mfma16(sh_frag_tr<true>(s_do, LDT, 32 * m + 4 * g, 32 * m + 16 + 4 * g, dt * 16, lane), pb, dv[dt]);
-          dk[dt] = mfma16(sh_frag_tr<true>(s_q, LDT, 32 * m + 4 * g, 32 * m + 16 + 4 * g, dt * 16, lane), dsb, dk[dt]);
+          dv[dt] = mfma16(lds_frag_tr(s_do, LDT, 32 * m + 4 * g, 32 * m + 16 + 4 * g, dt * 16, lane), pb, dv[dt]);
+          dk[dt] = mfma16(lds_frag_tr(s_q, LDT, 32 * m + 4 * g, 32 * m + 16 + 4 * g, dt * 16, lane), dsb, dk[dt]);
         }
       } else {
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
-          dv[dt] = mfma16(sh_frag_tr<false>(s_do, LDT, 32 * m + 4 * g, 0, dt * 16, lane), pb, dv[dt]);
-          dk[dt] = mfma16(sh_frag_tr<false>(s_q, LDT, 32 * m + 4 * g, 0, dt * 16, lane), dsb, dk[dt]);
+          dv[dt] = mfma16(sh_frag_tr_lo(s_do, LDT, 32 * m + 4 * g, dt * 16, lane), pb, dv[dt]);
+          dk[dt] = mfma16(sh_frag_tr_lo(s_q, LDT, 32 * m + 4 * g, dt * 16, lane), dsb, dk[dt]);
         }
       }
     }
@@ -375,13 +358,13 @@ __global__ __launch_bounds__(384) void attn_short_bwd_kernel(AttnArgs a) {
   if (w < NKT) {
     const int key = t * 16 + c;
     if (STAGED) {
-      if (t * 16 < a.Lk && !(a.dbg & 1)) {
+      if (t * 16 < a.Lk) {
         bf16_raw* dkp = (bf16_raw*)a.dk + (size_t)b * a.bsk + (size_t)(t * 16) * a.ldk + h * ATTN_D;
         bf16_raw* dvp = (bf16_raw*)a.dv + (size_t)b * a.bsv + (size_t)(t * 16) * a.ldv + h * ATTN_D;
         sh_store_tile(stage, dk, a.scale, dkp, a.ldk, a.Lk - t * 16, lane);
         sh_store_tile(stage, dv, 1.0f, dvp, a.ldv, a.Lk - t * 16, lane);
       }
-    } else if (key < a.Lk && !((a.dbg & 1) && lane != 0)) {
+    } else if (key < a.Lk) {
       bf16_raw* dkp = (bf16_raw*)a.dk + (size_t)b * a.bsk + (size_t)key * a.ldk + h * ATTN_D;
       bf16_raw* dvp = (bf16_raw*)a.dv + (size_t)b * a.bsv + (size_t)key * a.ldv + h * ATTN_D;
 #pragma unroll
@@ -401,24 +384,22 @@ __global__ __launch_bounds__(384) void attn_short_bwd_kernel(AttnArgs a) {
 #pragma unroll
     for (int m = 0; m < NCK; ++m) {
       if (2 * m + 1 < NKT) {
-        const bf16x8 dsf = sh_frag_tr<true>(s_ds, DS_LD, 32 * m + 4 * g, 32 * m + 16 + 4 * g, 16 * qt, lane);
+        const bf16x8 dsf = lds_frag_tr(s_ds, DS_LD, 32 * m + 4 * g, 32 * m + 16 + 4 * g, 16 * qt, lane);
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt)
-          dq[dt] = mfma16(sh_frag_tr<true>(s_k, LDT, 32 * m + 4 * g, 32 * m + 16 + 4 * g, dt * 16, lane), dsf, dq[dt]);
+          dq[dt] = mfma16(lds_frag_tr(s_k, LDT, 32 * m + 4 * g, 32 * m + 16 + 4 * g, dt * 16, lane), dsf, dq[dt]);
       } else {
-        const bf16x8 dsf = sh_frag_tr<false>(s_ds, DS_LD, 32 * m + 4 * g, 0, 16 * qt, lane);
+        const bf16x8 dsf = sh_frag_tr_lo(s_ds, DS_LD, 32 * m + 4 * g, 16 * qt, lane);
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt)
-          dq[dt] = mfma16(sh_frag_tr<false>(s_k, LDT, 32 * m + 4 * g, 0, dt * 16, lane), dsf, dq[dt]);
+          dq[dt] = mfma16(sh_frag_tr_lo(s_k, LDT, 32 * m + 4 * g, dt * 16, lane), dsf, dq[dt]);
       }
     }
     const int qrow = qt * 16 + c;
     if (STAGED) {
-      if (!(a.dbg & 1)) {
-        bf16_raw* dqp = (bf16_raw*)a.dq + (size_t)b * a.bsq + (size_t)(qt * 16) * a.ldq + h * ATTN_D;
-        sh_store_tile(stage, dq, a.scale, dqp, a.ldq, a.Lq - qt * 16, lane);
-      }
-    } else if (qrow < a.Lq && !((a.dbg & 1) && lane != 0)) {
+      bf16_raw* dqp = (bf16_raw*)a.dq + (size_t)b * a.bsq + (size_t)(qt * 16) * a.ldq + h * ATTN_D;
+      sh_store_tile(stage, dq, a.scale, dqp, a.ldq, a.Lq - qt * 16, lane);
+    } else if (qrow < a.Lq) {
       bf16_raw* dqp = (bf16_raw*)a.dq + (size_t)b * a.bsq + (size_t)qrow * a.ldq + h * ATTN_D;
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt)
@@ -454,10 +435,8 @@ int attn_short_fwd(const AttnArgs& a_in, bool bits_ready, hipStream_t st) {
   AttnArgs a = a_in;
   const int nqt = (a.Lq + 15) / 16, nkt = sh_round_tiles((a.Lk + 15) / 16);
   // waves (= query tiles) per workgroup: the whole query range when it is short; 7 tiles = 112 queries for long ones
-  // (441 BEV cells -> 4 workgroups per (batch, head)).  BEVBERT_SHORT_NW overrides (A/B measurements).
-  static const int env_nw = [] { const char* v = getenv("BEVBERT_SHORT_NW"); return v ? atoi(v) : 0; }();
-  int nw = nqt <= 6 ? nqt : 7;
-  if (env_nw >= 1 && env_nw <= 8) nw = env_nw < nqt ? env_nw : nqt;
+  // (441 BEV cells -> 4 workgroups per (batch, head))
+  const int nw = nqt <= 6 ? nqt : 7;
   a.nblk = (nqt + nw - 1) / nw;
   const int drop = a.drop_p > 0.f ? (bits_ready ? 2 : 1) : 0;
   const dim3 grid((unsigned)a.nblk * a.nh * a.B), block(64 * nw);
@@ -495,8 +474,6 @@ static void sh_launch_bwd_q(const AttnArgs& a, int nqt, dim3 grid, hipStream_t s
 
 int attn_short_bwd(const AttnArgs& a_in, hipStream_t st) {
   AttnArgs a = a_in;
-  static const int dbg = [] { const char* v = getenv("BEVBERT_SHORT_DBG"); return v ? atoi(v) : 0; }();
-  a.dbg = dbg;
   const int nqt = sh_round_tiles((a.Lq + 15) / 16), nkt = sh_round_tiles((a.Lk + 15) / 16);
   a.nblk = 1;
   const dim3 grid((unsigned)a.nh * a.B);

@@ -32,11 +32,6 @@
 #define SM_MAXKT 6      // 16-key tiles: Lk <= 96
 #define SM_DS_LD 40     // row stride (bf16) of the dS image: 32 queries + 8 (rows stay 8-byte aligned for the tr reads)
 
-__device__ __forceinline__ bf16x8 join_pair(uint2 a, uint2 b) { return as_bf16x8(make_uint4(a.x, a.y, b.x, b.y)); }
-__device__ __forceinline__ uint2 pack4(const f32x4& v) {
-  return make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
-}
-
 // =============================================================================================
 // Forward.  Workgroup = NW waves of one (batch, head, query block); wave w owns the 16-query tiles
 // (blk * NW + w) * qpw .. + qpw - 1.
@@ -169,14 +164,6 @@ template <int NKT> struct SmLds {
   static constexpr int bytes = stat_off + 2 * 32 * 4;
 };
 
-template <int CTRL> __device__ __forceinline__ float sm_dpp(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float sm_sum8(float v) {   // sum over the 8 lanes that hold one row of a staged tile
-  v += sm_dpp<0xB1>(v);           // quad_perm [1,0,3,2]
-  v += sm_dpp<0x4E>(v);           // quad_perm [2,3,0,1]
-  return v + sm_dpp<0x141>(v);    // row_half_mirror: lane i <-> 7 - i of its half row
-}
 
 template <int NKT, bool DROP, bool KMASK>
 __global__ __launch_bounds__(64, 1) void attn_small_bwd_kernel(AttnArgs a) {
@@ -244,7 +231,7 @@ __global__ __launch_bounds__(64, 1) void attn_small_bwd_kernel(AttnArgs a) {
       for (int j = 0; j < 4; ++j)
         dsum += __uint_as_float(dw[j] << 16) * __uint_as_float(ow[j] << 16) +
                 __uint_as_float(dw[j] & 0xffff0000u) * __uint_as_float(ow[j] & 0xffff0000u);
-      dsum = sm_sum8(dsum);
+      dsum = sum8(dsum);
       if ((lane & 7) == 0) s_dlt[row] = dsum;
     }
     if (lane < 32) s_lse2[lane] = (q0 + lane < a.Lq) ? r.lse * LOG2E : INFINITY;
@@ -437,7 +424,7 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(5))) void a
     for (int j = 0; j < 4; ++j)
       dsum += __uint_as_float(dw[j] << 16) * __uint_as_float(ow[j] << 16) +
               __uint_as_float(dw[j] & 0xffff0000u) * __uint_as_float(ow[j] & 0xffff0000u);
-    dsum = sm_sum8(dsum);
+    dsum = sum8(dsum);
     if ((lane & 7) == 0) s_dlt[row] = dsum;
   }
   if (tid < SM2_ROWS) {
@@ -592,21 +579,12 @@ static void launch_bwd(const AttnArgs& a, dim3 grid, hipStream_t st) {
   else hipLaunchKernelGGL((attn_small_bwd_kernel<NKT, false, false>), grid, dim3(64), 0, st, a);
 }
 
-static int sm_env(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return (v && v[0] >= '1' && v[0] <= '8') ? v[0] - '0' : dflt;
-}
-
 int attn_small_fwd(const AttnArgs& a_in, hipStream_t st) {
   AttnArgs a = a_in;
   const int nqt = (a.Lq + 15) / 16, nkt = (a.Lk + 15) / 16;
-  // waves per workgroup / query tiles per wave (BEVBERT_SMALL_NW / BEVBERT_SMALL_QPW for A/B measurements):
-  // short query sequences get one tile per wave (the whole (batch, head) in one workgroup), long ones (the 441 BEV
-  // cells against the text) four waves of two tiles
-  static const int env_nw = sm_env("BEVBERT_SMALL_NW", 0), env_qpw = sm_env("BEVBERT_SMALL_QPW", 0);
-  int nw = nqt <= 6 ? nqt : 4, qpw = nqt <= 6 ? 1 : 2;
-  if (env_nw) nw = env_nw < nqt ? env_nw : nqt;
-  if (env_qpw) qpw = env_qpw;
+  // waves per workgroup / query tiles per wave: short query sequences get one tile per wave (the whole (batch, head)
+  // in one workgroup), long ones (the 441 BEV cells against the text) four waves of two tiles
+  const int nw = nqt <= 6 ? nqt : 4, qpw = nqt <= 6 ? 1 : 2;
   a.nblk = (nqt + nw * qpw - 1) / (nw * qpw);
   const dim3 grid((unsigned)a.nblk * a.nh * a.B), block(64 * nw);
   if (nkt <= 2) launch_fwd<2>(a, grid, block, qpw, st);
