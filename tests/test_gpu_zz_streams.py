@@ -593,3 +593,143 @@ def test_gradient_exchange_moves_to_a_group_of_its_own_when_the_default_group_wa
     red.finish()
     torch.cuda.synchronize()
     assert torch.equal(flat, want)                 # one rank: the sum over ranks is the tensor itself
+
+
+# ----------------------------------------------------------------------------- capture.py: one capture-and-recover path
+# (a Python exception raised while a capture is open, as in the failed-capture test above: nothing here faults the device)
+def test_capture_records_without_running_and_graphs_of_one_pool_replay_in_turn(env):
+    from vln_bevbert_amd import capture
+    x, y = torch.arange(8.0, device=DEV), torch.zeros(8, device=DEV)
+    g1, res = capture.capture(lambda: y.copy_(x * 2))
+    torch.cuda.synchronize()
+    assert res is y and not bool(y.any())                        # recorded, not run: the caller replays
+    x.add_(1)
+    g1.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(y, torch.arange(1.0, 9.0, device=DEV) * 2)
+    x2, y2 = torch.full((8,), 5.0, device=DEV), torch.zeros(8, device=DEV)
+    g2, _ = capture.capture(lambda: y2.copy_(x2 * 2), pool=g1.pool())
+    assert g2.pool() == g1.pool()
+    x.fill_(3)
+    g1.replay()
+    g2.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(y, torch.full((8,), 6.0, device=DEV)) and torch.equal(y2, torch.full((8,), 10.0, device=DEV))
+
+
+def test_a_failed_capture_with_an_open_fork_is_ended_and_leaves_nothing_behind(env):
+    """The body forks a side stream that only ``extra_streams`` names, queues deferred work the way a backward pass does, and
+    raises with the fork still open: ``capture`` joins it, ends the capture, drops the queued work and reports."""
+    from vln_bevbert_amd import capture, lib, ops
+    from vln_bevbert_amd.hwqueues import side_stream
+    side = side_stream(DEV)
+    x, z, ran = torch.arange(8.0, device=DEV), torch.zeros(8, device=DEV), []
+    sentinel, record, made = (lambda: ran.append(1)), (0, 1, 1, 8, 0, 0, 0, 1), []
+
+    def body():
+        assert torch.cuda.is_current_stream_capturing()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            z.add_(1)
+        h = lib.stream()
+        if h not in ops.WgradStream._pending:
+            made.append(h)
+            ops.WgradStream._pending[h] = (torch.cuda.current_stream(), [])
+        ops.WgradStream._pending[h][1].append(sentinel)
+        ops.ReduceQueue.jobs.append(record)
+        raise RuntimeError("injected")
+
+    try:
+        with pytest.raises(capture.CaptureFailed) as info:
+            capture.capture(body, extra_streams=[side])
+        assert "injected" in info.value.message and len(info.value.message) <= 400
+        assert isinstance(info.value.__cause__, RuntimeError) and "injected" in str(info.value.__cause__)
+        assert not torch.cuda.is_current_stream_capturing()
+        assert ops.ReduceQueue.jobs == [] and ops.ReduceQueue.accum_jobs == []
+        assert not any(fns for _, fns in ops.WgradStream._pending.values())
+        ops.WgradStream.flush_all()                              # what the next backward pass does with deferred work
+        assert ran == []
+        y = x + 1
+        torch.cuda.synchronize()
+        assert torch.equal(y, torch.arange(1.0, 9.0, device=DEV)) and not bool(z.any())
+        g, _ = capture.capture(lambda: z.copy_(x * 2))
+        g.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(z, x * 2)
+    finally:                                                     # whatever failed above, the next test starts clean
+        ops.ReduceQueue.jobs = [j for j in ops.ReduceQueue.jobs if j is not record]
+        for _, fns in ops.WgradStream._pending.values():
+            fns[:] = [f for f in fns if f is not sentinel]
+        for h in made:
+            ops.WgradStream._pending.pop(h, None)
+
+
+def test_nav_graph_runner_goes_on_eagerly_after_a_failed_capture(env):
+    from types import SimpleNamespace
+    from vln_bevbert_amd.nav_static import NavGraphRunner
+    runner = NavGraphRunner(SimpleNamespace(training=False, vln_bert=None), eager_uses=1)
+
+    def fn(x):
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("injected " + "x" * 600)
+        return {"o": x["a"] * 3}
+
+    for i in range(3):                                           # eager, capture (fails, eager), eager
+        a = torch.full((2, 8), float(i + 1), device=DEV)
+        out = runner._run(("k", 2, 8), {"a": a}, fn)
+        torch.cuda.synchronize()
+        assert torch.equal(out["o"], a * 3), i
+        assert not torch.cuda.is_current_stream_capturing()
+        assert runner.stats == {"replays": 0, "eager": i + 1, "captures": 0}
+        assert (runner.graph_error is None) == (i == 0)
+    assert "injected" in runner.graph_error and len(runner.graph_error) <= 400
+    assert runner.captured_graphs() == 0 and len(runner.buckets) == 1
+
+
+def test_nav_train_runner_drops_every_graph_after_a_failed_capture_and_trains_on_eagerly(env):
+    """Two segments per episode, o1 = a * w and o2 = o1 * w, one backward through both.  With graphs the second episode is
+    the capture episode: segment 1's forward is captured, segment 2's raises.  That episode trains nothing (as a capture
+    episode never does) and keeps no graph -- a backward graph of segment 1 alone would later replay against a forward
+    that no longer exists -- and the episodes before and after it leave exactly the gradients of a runner without graphs."""
+    from types import SimpleNamespace
+    from vln_bevbert_amd.nav_static import NavTrainRunner
+    grads = {}
+    for graphs in (False, True):
+        w = torch.linspace(0.5, 2.0, 16, device=DEV).view(2, 8).requires_grad_(True)
+        runner = NavTrainRunner(SimpleNamespace(training=True, vln_bert=None), SimpleNamespace(sync=lambda: None),
+                                eager_uses=1, graphs=graphs)
+
+        def fn1(x):
+            return {"o": x["a"] * w}
+
+        def fn2(x):
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("injected")
+            return {"o": x["a"] * w}
+
+        for ep in range(3):
+            a = (torch.arange(16.0, device=DEV).view(2, 8) + ep).requires_grad_(True)
+            w.grad = None
+            runner.begin_episode()
+            capture_episode = runner.capturing
+            assert capture_episode == (graphs and ep == 1)
+            o1 = runner._segment("navigation", (2, 8), {"a": a}, ("a",), fn1, {}, ("o",))["o"]
+            o2 = runner._segment("navigation", (2, 8), {"a": o1}, ("a",), fn2, {}, ("o",))["o"]
+            torch.cuda.synchronize()
+            assert torch.equal(o2, a.detach() * w.detach() * w.detach())
+            if capture_episode:
+                runner.end_capture()
+                assert w.grad is None and a.grad is None
+                assert "injected" in runner.graph_error and "injected" in runner.graph_traceback
+                assert "fn2" in runner.graph_traceback
+            else:
+                (o2 * o2).sum().backward()
+                torch.cuda.synchronize()
+                grads[(graphs, ep)] = (w.grad.clone(), a.grad.clone())
+            assert not runner.capturing and not torch.cuda.is_current_stream_capturing()
+            assert len(runner.segs) == 2 and all(s.fwd is None and s.bwd is None for s in runner.segs.values())
+        assert runner.captured_graphs() == 0
+        assert runner.stats["captures"] == (1 if graphs else 0) and runner.stats["replays"] == 0
+    for ep in (0, 2):
+        for got, want in zip(grads[(True, ep)], grads[(False, ep)]):
+            assert float(want.abs().sum()) > 0 and torch.equal(got, want), ep

@@ -1079,6 +1079,91 @@ def test_nav_graph_runner_clears_stale_padding_after_a_full_width_fill():
         assert float(got["gmap_pair_dists"][:, :, G:].abs().max() if G < 8 else 0.0) == 0.0
 
 
+def test_static_inputs_fill_clears_what_a_wider_fill_left_and_only_then():
+    """capture.StaticInputs.fill, the one fill routine of both navigation runners, on the object itself: the sequence of the
+    runner test above, with the ``zero_`` calls counted -- none on the first fill and on a fill of the buffer's own shape,
+    one when the last fill was wider."""
+    from vln_bevbert_amd.capture import StaticInputs
+
+    class Counted(torch.Tensor):
+        zeroed = 0
+
+        def zero_(self):
+            Counted.zeroed += 1
+            return super().zero_()
+
+    si = StaticInputs({"gmap_masks": torch.ones(2, 5, dtype=torch.bool), "gmap_pair_dists": torch.ones(2, 5, 5)},
+                      {"gmap_masks": (2, 8), "gmap_pair_dists": (2, 8, 8)})
+    assert si.bufs["gmap_masks"].shape == (2, 8) and si.bufs["gmap_masks"].dtype == torch.bool
+    assert si.bufs["gmap_pair_dists"].shape == (2, 8, 8) and si.bufs["gmap_pair_dists"].dtype == torch.float32
+    assert not any(bool(b.any()) for b in si.bufs.values())
+    si.bufs = {k: b.as_subclass(Counted) for k, b in si.bufs.items()}
+    for G, zeroed in ((5, 0), (8, 0), (6, 2), (8, 0), (3, 2)):             # two buffers
+        Counted.zeroed = 0
+        si.fill("gmap_masks", torch.ones(2, G, dtype=torch.bool))
+        si.fill("gmap_pair_dists", torch.full((2, G, G), float(G)))
+        assert Counted.zeroed == zeroed, (G, Counted.zeroed)
+        assert si.filled == {"gmap_masks": (2, G), "gmap_pair_dists": (2, G, G)}
+        got = {k: b.as_subclass(torch.Tensor) for k, b in si.bufs.items()}
+        assert bool(got["gmap_masks"][:, :G].all()) and not bool(got["gmap_masks"][:, G:].any()), G
+        assert float(got["gmap_pair_dists"][:, :G, :G].min()) == G
+        assert float(got["gmap_pair_dists"][:, G:].abs().max() if G < 8 else 0.0) == 0.0
+        assert float(got["gmap_pair_dists"][:, :, G:].abs().max() if G < 8 else 0.0) == 0.0
+
+
+@pytest.mark.parametrize("with_text", [False, True])
+def test_navigation_call_pads_the_shapes_and_builds_the_keys_of_both_runners(with_text):
+    """nav_static.NavGraphRunner._navigation_call, the one builder of a navigation step's feeds: B = 2, G = 5 nodes, C = 3
+    candidates, L = 4 tokens, 9 BEV cells.  Node and candidate axes are padded to 8; the key is the tuple both runners have
+    always built for these sizes (bucket and segment counts hang on it); the fusion table is sap_fusion_indices' own."""
+    from types import SimpleNamespace
+    from vln_bevbert_amd.nav_static import NavGraphRunner
+    from vln_bevbert_amd.pretrain_cmt import sap_fusion_indices
+    B, G, C, L, H = 2, 5, 3, 4, 6
+    g = torch.Generator().manual_seed(3)
+    visited = torch.tensor([[True, True, False, False, True], [True, False, False, True, False]])
+    nav = {"txt_embeds": torch.randn(B, L, H, generator=g), "txt_masks": torch.ones(B, L, dtype=torch.bool),
+           "gmap_img_embeds": torch.randn(B, G, H, generator=g), "gmap_step_ids": torch.randint(0, 9, (B, G), generator=g),
+           "gmap_pos_fts": torch.randn(B, G, 7, generator=g), "gmap_masks": torch.ones(B, G, dtype=torch.bool),
+           "gmap_pair_dists": torch.rand(B, G, G, generator=g), "gmap_visited_masks": visited,
+           "gmap_visited_masks_cpu": visited.clone(), "bev_fts": torch.randn(B, 9, H, generator=g),
+           "bev_pos_fts": torch.randn(B, 9, 3, generator=g), "bev_nav_masks": torch.ones(B, 9, dtype=torch.bool),
+           "bev_cand_idxs": torch.randint(0, 9, (B, C), generator=g),
+           "gmap_vpids": [[None, "a", "b", "c", "d"], [None, "p", "q", "r", "s"]],
+           "bev_cand_vpids": [[None, "b", "d"], [None, "r", "q"]]}
+    runner = NavGraphRunner(SimpleNamespace(training=False, vln_bert=None))
+    feeds, shapes, key, sizes = runner._navigation_call(nav, with_text=with_text)
+    assert key == (2, 8, 8, 4, 9) and sizes == (5, 3)
+    assert shapes == {"gmap_img_embeds": (2, 8, 6), "gmap_step_ids": (2, 8), "gmap_pos_fts": (2, 8, 7), "gmap_masks": (2, 8),
+                      "gmap_pair_dists": (2, 8, 8), "gmap_visited_masks": (2, 8), "bev_cand_idxs": (2, 8)}
+    names = ["gmap_img_embeds", "gmap_step_ids", "gmap_pos_fts", "gmap_masks", "gmap_pair_dists", "gmap_visited_masks",
+             "bev_fts", "bev_pos_fts", "bev_nav_masks", "bev_cand_idxs", "src", "vis_c"]
+    assert list(feeds) == (["txt_embeds", "txt_masks"] if with_text else []) + names
+    assert all(feeds[k] is nav[k] for k in feeds if k not in ("src", "vis_c"))
+    src, vis_c = sap_fusion_indices(nav["gmap_vpids"], visited.tolist(), nav["bev_cand_vpids"], 8, 8)
+    assert src.shape == (2, 8) and vis_c.shape == (2, 8) and vis_c.any() and (src[:, 1:5] < 9).any()
+    assert torch.equal(feeds["src"], torch.from_numpy(src)) and torch.equal(feeds["vis_c"], torch.from_numpy(vis_c))
+    # the key each ``navigation`` method makes of it (the inference runner's bucket; the training runner's segment, in front
+    # of which ``_segment`` puts the mode and the step index), and what it hands back of the padded outputs
+    from vln_bevbert_amd.nav_static import NavTrainRunner
+    out = {"gmap_embeds": torch.zeros(2, 8, H), "global_logits": torch.zeros(2, 8), "local_logits": torch.zeros(2, 8),
+           "fused_logits": torch.zeros(2, 8)}
+    seen = []
+    if with_text:
+        nav["txt_embeds"].requires_grad_(True)
+        runner = NavTrainRunner(SimpleNamespace(training=True, vln_bert=None), None)
+        runner._segment = lambda mode, key, feeds, *a: seen.append(((mode,) + key, list(feeds))) or out
+        want = ("navigation", 2, 8, 8, 4, 9, ("txt_embeds",))
+    else:
+        runner._text_inputs = lambda *a: {}
+        runner._run = lambda key, feeds, *a: seen.append((key, list(feeds))) or out
+        want = ("navigation", 2, 8, 8, 4, 9)
+    got = runner.navigation(nav)
+    assert seen == [(want, list(feeds))]
+    assert {k: v if v is None else tuple(v.shape) for k, v in got.items()} == {
+        "gmap_embeds": (2, 5, H), "global_logits": (2, 5), "local_logits": (2, 3), "fused_logits": (2, 5), "obj_logits": None}
+
+
 def test_device_graph_map_host_side_against_the_host_map(monkeypatch):
     """graph_map_dev.DeviceGraphMap without the device: its host half (observation digest, id -> node lookups, node order,
     what it ships to the kernels) on CPU tensors with the C-ABI launches recorded instead of run, against

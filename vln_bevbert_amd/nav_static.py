@@ -20,6 +20,7 @@ use.  Outputs are views of static buffers: they are valid until the next call of
 import numpy as np
 import torch
 
+from . import capture
 from .graph_map import HostFeed
 from .pretrain_cmt import fuse_sap_logits, sap_fusion_indices
 
@@ -29,9 +30,14 @@ def _pad_to(n, step):
 
 
 class _Bucket:
-    def __init__(self):
-        self.inputs, self.outputs, self.graph, self.uses = {}, None, None, 0
-        self.filled = {}          # name -> shape of the last (smaller than the buffer) tensor written into the buffer
+    def __init__(self, inputs):
+        self.inputs, self.outputs, self.graph, self.uses = inputs, None, None, 0
+
+
+def _slice_outputs(out, G, C):
+    """The navigation outputs without the padding of the node / candidate axes."""
+    return {"gmap_embeds": out["gmap_embeds"][:, :G], "global_logits": out["global_logits"][:, :G],
+            "local_logits": out["local_logits"][:, :C], "fused_logits": out["fused_logits"][:, :G], "obj_logits": None}
 
 
 class NavGraphRunner:
@@ -59,51 +65,31 @@ class NavGraphRunner:
         replay its graph, return its (static) outputs.  ``static``: name -> buffer the caller keeps up to date itself
         (shared by every bucket: the instruction's tensors change once per episode, not per step)."""
         assert not self.model.training, "NavGraphRunner serves inference rollouts (model.eval())"
-        shapes = shapes or {}
         b = self.buckets.get(key)
         if b is None:
-            b = self.buckets[key] = _Bucket()
-            b.inputs = {k: torch.zeros(shapes.get(k, v.shape), dtype=v.dtype, device=v.device) for k, v in feeds.items()}
-            b.inputs.update(static or {})         # buffers that are filled elsewhere (once per episode), not per call
+            b = self.buckets[key] = _Bucket(capture.StaticInputs(feeds, shapes or {}))
+            b.inputs.bufs.update(static or {})    # buffers that are filled elsewhere (once per episode), not per call
         for k, v in feeds.items():
-            buf = b.inputs[k]
-            if v.shape == buf.shape:
-                buf.copy_(v, non_blocking=True)
-                b.filled[k] = tuple(v.shape)      # a later, smaller fill must clear what this one wrote (ADVICE r3)
-                continue
-            last = b.filled.get(k)
-            if last is not None and any(l > n for l, n in zip(last, v.shape)):
-                buf.zero_()                       # the map shrank (a new episode): clear what the last fill left behind
-            buf[tuple(slice(0, n) for n in v.shape)].copy_(v, non_blocking=True)
-            b.filled[k] = tuple(v.shape)
+            b.inputs.fill(k, v)
         b.uses += 1
         if b.graph is not None:
             b.graph.replay()
             self.stats["replays"] += 1
             return b.outputs
-        if b.uses <= self.eager_uses or self.graph_error is not None:
+        with torch.no_grad():
+            if b.uses > self.eager_uses and self.graph_error is None:
+                try:
+                    b.graph, b.outputs = capture.capture(lambda: fn(b.inputs.bufs), self.pool)
+                except capture.CaptureFailed as e:      # a refused capture is reported, the rollout goes on eagerly
+                    self.graph_error = e.message
+                else:
+                    self.pool = b.graph.pool()
+                    self.stats["captures"] += 1
+                    b.graph.replay()
+                    self.stats["replays"] += 1
+                    return b.outputs
             self.stats["eager"] += 1
-            with torch.no_grad():
-                return fn(b.inputs)
-        try:
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.no_grad(), torch.cuda.graph(g, pool=self.pool, capture_error_mode="thread_local"):
-                out = fn(b.inputs)
-            self.pool = self.pool or g.pool()
-            b.graph, b.outputs = g, out
-            self.stats["captures"] += 1
-            g.replay()
-            self.stats["replays"] += 1
-            return out
-        except Exception as e:      # noqa: BLE001 -- a refused capture is reported, the rollout goes on eagerly
-            self.graph_error = f"{type(e).__name__}: {e}"
-            from . import lib
-            lib.load().bevbert_hip_error_reset()
-            torch.cuda.synchronize()
-            self.stats["eager"] += 1
-            with torch.no_grad():
-                return fn(b.inputs)
+            return fn(b.inputs.bufs)
 
     # ------------------------------------------------------------------------------------------------ panorama
     def panorama(self, batch):
@@ -126,29 +112,29 @@ class NavGraphRunner:
         if nav.get("obj_embeds") is not None:
             with torch.no_grad():
                 return self.model("navigation", nav)
+        feeds, shapes, key, (G, C) = self._navigation_call(nav, with_text=False)
+        static = self._text_inputs(nav["txt_embeds"], nav["txt_masks"])
+        return _slice_outputs(self._run(("navigation",) + key, feeds, self._navigation_device, shapes, static), G, C)
+
+    def _navigation_call(self, nav, with_text):
+        """What a navigation step feeds its static buffers: (feeds, padded buffer shapes, shape-bucket key, (G, C)).  The
+        host's share of the step is done here: the fusion index table of the (padded) node and candidate axes."""
         B, G = nav["gmap_masks"].shape
         C = nav["bev_cand_idxs"].shape[1]
         Gp, Cp = _pad_to(G, self.g_step), _pad_to(C, self.c_step)
         vis_host = nav.get("gmap_visited_masks_cpu")
         vis_host = (vis_host if vis_host is not None else nav["gmap_visited_masks"].cpu()).tolist()
         src, vis_c = sap_fusion_indices(nav["gmap_vpids"], vis_host, nav["bev_cand_vpids"], Gp, Cp)
-        dev = nav["gmap_masks"].device
         if self.feed is None:
-            self.feed = HostFeed.shared(dev)
-        idx = self.feed({"src": src, "vis_c": vis_c})
+            self.feed = HostFeed.shared(nav["gmap_masks"].device)
         names = ("gmap_img_embeds", "gmap_step_ids", "gmap_pos_fts", "gmap_masks",
                  "gmap_pair_dists", "gmap_visited_masks", "bev_fts", "bev_pos_fts", "bev_nav_masks", "bev_cand_idxs")
-        feeds = {k: nav[k] for k in names}
-        static = self._text_inputs(nav["txt_embeds"], nav["txt_masks"])
-        feeds.update(src=idx["src"], vis_c=idx["vis_c"])
+        feeds = {k: nav[k] for k in (("txt_embeds", "txt_masks") if with_text else ()) + names}
+        feeds.update(self.feed({"src": src, "vis_c": vis_c}))
         shapes = {"gmap_img_embeds": (B, Gp, nav["gmap_img_embeds"].shape[2]), "gmap_step_ids": (B, Gp),
                   "gmap_pos_fts": (B, Gp, nav["gmap_pos_fts"].shape[2]), "gmap_masks": (B, Gp),
                   "gmap_pair_dists": (B, Gp, Gp), "gmap_visited_masks": (B, Gp), "bev_cand_idxs": (B, Cp)}
-        key = ("navigation", B, Gp, Cp, nav["txt_embeds"].shape[1], nav["bev_fts"].shape[1])
-        out = self._run(key, feeds, self._navigation_device, shapes, static)
-        return {"gmap_embeds": out["gmap_embeds"][:, :G], "global_logits": out["global_logits"][:, :G],
-                "local_logits": out["local_logits"][:, :C], "fused_logits": out["fused_logits"][:, :G],
-                "obj_logits": None}
+        return feeds, shapes, (B, Gp, Cp, nav["txt_embeds"].shape[1], nav["bev_fts"].shape[1]), (G, C)
 
     def _text_inputs(self, txt_embeds, txt_masks):
         """Static buffers of the instruction: its states and mask, and their K|V projections for every cross-attention
@@ -231,10 +217,10 @@ class NavGraphRunner:
 # The capture episode does not train (nothing of its backward executes).  From then on episodes whose segments all have
 # graphs replay them; a segment without one (a new shape bucket) runs eagerly.
 class _TrainSeg:
-    def __init__(self, key):
-        self.key, self.inputs, self.diff, self.fn = key, {}, (), None
+    def __init__(self, key, inputs):
+        self.key, self.inputs, self.diff, self.fn = key, inputs, (), None
         self.outs, self.out_names, self.grad_outs, self.grad_ins = None, (), None, None
-        self.fwd, self.bwd, self.uses, self.filled = None, None, 0, {}
+        self.fwd, self.bwd, self.uses = None, None, 0
 
 
 class _GradTap(torch.autograd.Function):
@@ -261,7 +247,7 @@ class _SegFn(torch.autograd.Function):
         # reads features only) must still be a node of the autograd graph, or its parameter gradients would never be issued
         with torch.no_grad():
             for name, x in zip(seg.diff, diff_tensors):
-                runner._fill(seg, name, x)
+                seg.inputs.fill(name, x)
         if seg.fwd is not None:
             seg.fwd.replay()
             runner.stats["replays"] += 1
@@ -295,7 +281,6 @@ class NavTrainRunner(NavGraphRunner):
         self.arena, self.graphs = arena, graphs
         self.segs, self.episode, self.capturing = {}, 0, False
         self._order, self._t = [], {"panorama": 0, "navigation": 0}
-        self._pool = None
         self._anchor = None
 
     # ---- episode protocol
@@ -314,42 +299,26 @@ class NavTrainRunner(NavGraphRunner):
         try:
             for seg in reversed(self._order):
                 self._capture_backward(seg)
-        except Exception as e:      # noqa: BLE001 -- a refused capture is reported, training goes on eagerly
+        except capture.CaptureFailed as e:
             self._capture_failed(e)
-        self.capturing = False
-        self._order = []
+        self.capturing, self._order = False, []
 
     def _capture_failed(self, e):
+        """A refused capture is reported and training goes on eagerly, for good: graphs of one pool are only sound as the
+        whole set, replayed in the order of their capture, so the ones made so far go, and this episode makes no more."""
         import traceback
-        self.graph_error = f"{type(e).__name__}: {e}"[:400]
-        self.graph_traceback = "".join(traceback.format_exception(type(e), e, e.__traceback__))[-3000:]
-        from . import lib, ops
-        if torch.cuda.is_current_stream_capturing():
-            ops.join_captured_side_streams()
-        lib.load().bevbert_hip_error_reset()
-        torch.cuda.synchronize()
-        ops.WgradStream.drop_pending()
-        ops.ReduceQueue.drop_pending()
+        cause = e.__cause__
+        self.graph_error = e.message
+        self.graph_traceback = "".join(traceback.format_exception(type(cause), cause, cause.__traceback__))[-3000:]
         for seg in self.segs.values():
             seg.fwd = seg.bwd = None
+        self.capturing, self._order = False, []
 
     # ---- plumbing
-    def _fill(self, seg, name, v):
-        buf = seg.inputs[name]
-        if v.shape == buf.shape:
-            buf.copy_(v, non_blocking=True)
-            seg.filled[name] = tuple(v.shape)
-            return
-        last = seg.filled.get(name)
-        if last is not None and any(l > n for l, n in zip(last, v.shape)):
-            buf.zero_()
-        buf[tuple(slice(0, n) for n in v.shape)].copy_(v, non_blocking=True)
-        seg.filled[name] = tuple(v.shape)
-
     @staticmethod
     def _tapped(seg):
         seg.grad_ins = {}
-        return {k: (_GradTap.apply(v, seg, k) if k in seg.diff else v) for k, v in seg.inputs.items()}
+        return {k: (_GradTap.apply(v, seg, k) if k in seg.diff else v) for k, v in seg.inputs.bufs.items()}
 
     def _forward_eager(self, seg):
         with torch.enable_grad():
@@ -379,27 +348,10 @@ class NavTrainRunner(NavGraphRunner):
         return seg.grad_ins                    # both modes: the arena sees the same additions in the same order
 
     def _captured(self, body):
-        """Run ``body`` inside a stream capture; an exception inside it is carried OUT of the capture (with every forked side
-        stream joined first: a capture with unjoined forks cannot end, and the stream would stay in capture mode)."""
-        from . import ops
-        torch.cuda.synchronize()
-        if self._pool is None:
-            self._pool = torch.cuda.graph_pool_handle()
-        g = torch.cuda.CUDAGraph()
-        err = None
-        try:
-            with torch.cuda.graph(g, pool=self._pool, capture_error_mode="thread_local"):
-                try:
-                    body()
-                except Exception as e:      # noqa: BLE001
-                    err = e
-                    ops.join_captured_side_streams()
-        except Exception as e:      # noqa: BLE001 -- ending the capture failed as well
-            err = err or e
-        if err is not None:
-            raise err
+        graph, _ = capture.capture(body, self.pool)
+        self.pool = graph.pool()
         self.stats["captures"] += 1
-        return g
+        return graph
 
     def _capture_forward(self, seg):
         def body():
@@ -425,26 +377,25 @@ class NavTrainRunner(NavGraphRunner):
         key = (mode, t) + tuple(key)
         seg = self.segs.get(key)
         if seg is None:
-            seg = self.segs[key] = _TrainSeg(key)
+            seg = self.segs[key] = _TrainSeg(key, capture.StaticInputs(feeds, shapes))
             seg.diff, seg.fn, seg.out_names = tuple(diff), fn, tuple(out_names)
-            for k, v in feeds.items():
-                buf = torch.zeros(shapes.get(k, v.shape), dtype=v.dtype, device=v.device)
-                seg.inputs[k] = buf.requires_grad_(True) if k in diff else buf
+            for k in seg.diff:
+                seg.inputs.bufs[k].requires_grad_(True)
         seg.uses += 1
         with torch.no_grad():
             for k, v in feeds.items():
                 if k not in seg.diff:
-                    self._fill(seg, k, v)
+                    seg.inputs.fill(k, v)
         if self.capturing and seg.fwd is None:
             try:
                 with torch.no_grad():
                     for k in seg.diff:
-                        self._fill(seg, k, feeds[k])
+                        seg.inputs.fill(k, feeds[k])
                 self._capture_forward(seg)
                 # (leaves that require grad where the real outputs do: the glue behind them -- the map's functional update
                 # path, the choice of the next segments' differentiable inputs -- must see what a training episode sees)
                 return {n: seg.outs[n].detach().requires_grad_(seg.outs[n].requires_grad) for n in seg.out_names}
-            except Exception as e:      # noqa: BLE001
+            except capture.CaptureFailed as e:
                 self._capture_failed(e)
         if self._anchor is None:
             self._anchor = torch.zeros((), device=next(iter(feeds.values())).device, requires_grad=True)
@@ -468,24 +419,8 @@ class NavTrainRunner(NavGraphRunner):
     def navigation(self, nav):
         if nav.get("obj_embeds") is not None:
             return self.model("navigation", nav)
-        B, G = nav["gmap_masks"].shape
-        C = nav["bev_cand_idxs"].shape[1]
-        Gp, Cp = _pad_to(G, self.g_step), _pad_to(C, self.c_step)
-        vis_host = nav.get("gmap_visited_masks_cpu")
-        vis_host = (vis_host if vis_host is not None else nav["gmap_visited_masks"].cpu()).tolist()
-        src, vis_c = sap_fusion_indices(nav["gmap_vpids"], vis_host, nav["bev_cand_vpids"], Gp, Cp)
-        dev = nav["gmap_masks"].device
-        if self.feed is None:
-            self.feed = HostFeed.shared(dev)
-        idx = self.feed({"src": src, "vis_c": vis_c})
-        names = ("txt_embeds", "txt_masks", "gmap_img_embeds", "gmap_step_ids", "gmap_pos_fts", "gmap_masks",
-                 "gmap_pair_dists", "gmap_visited_masks", "bev_fts", "bev_pos_fts", "bev_nav_masks", "bev_cand_idxs")
-        feeds = {k: nav[k] for k in names}
+        feeds, shapes, key, (G, C) = self._navigation_call(nav, with_text=True)
         feeds["gmap_img_embeds"] = feeds["gmap_img_embeds"].to(nav["txt_embeds"].dtype)
-        feeds.update(src=idx["src"], vis_c=idx["vis_c"])
-        shapes = {"gmap_img_embeds": (B, Gp, nav["gmap_img_embeds"].shape[2]), "gmap_step_ids": (B, Gp),
-                  "gmap_pos_fts": (B, Gp, nav["gmap_pos_fts"].shape[2]), "gmap_masks": (B, Gp),
-                  "gmap_pair_dists": (B, Gp, Gp), "gmap_visited_masks": (B, Gp), "bev_cand_idxs": (B, Cp)}
         diff = tuple(k for k in ("txt_embeds", "gmap_img_embeds") if feeds[k].requires_grad)
         drop = self.model
 
@@ -494,11 +429,9 @@ class NavTrainRunner(NavGraphRunner):
             from . import ops
             y["bev_fts"] = ops.dropout(x["bev_fts"], drop.feat_dropout, True)        # VLNBert.forward('navigation'), model.py:36
             return self._navigation_device(y)
-        key = (B, Gp, Cp, nav["txt_embeds"].shape[1], nav["bev_fts"].shape[1], diff)
-        out = self._segment("navigation", key, feeds, diff, fn, shapes,
+        out = self._segment("navigation", key + (diff,), feeds, diff, fn, shapes,
                             ("gmap_embeds", "global_logits", "local_logits", "fused_logits"))
-        return {"gmap_embeds": out["gmap_embeds"][:, :G], "global_logits": out["global_logits"][:, :G],
-                "local_logits": out["local_logits"][:, :C], "fused_logits": out["fused_logits"][:, :G], "obj_logits": None}
+        return _slice_outputs(out, G, C)
 
     def captured_graphs(self):
         return sum((s.fwd is not None) + (s.bwd is not None) for s in self.segs.values())

@@ -21,7 +21,8 @@ from .ops_core import (  # noqa: F401
     _LT_WS_BYTES, _Runtime, _UseParam, _compute, _drop_bits_words, _f32, _gemm, _hash32,
     _mark_touched, _sink, call, use_param)
 from .ops_reduce import (  # noqa: F401
-    ReduceQueue, SCRATCH, ScratchRing, WgradStream, _PARTIAL_ROWS, _on_launch_stream, _partial_rows, join_captured_side_streams)
+    ReduceQueue, SCRATCH, ScratchRing, WgradStream, _PARTIAL_ROWS, _on_launch_stream, _partial_rows)
+from .capture import join_captured_side_streams  # noqa: F401
 from .ops_gemm import (  # noqa: F401
     GEMM_FALLBACKS, GEMM_TUNING_FILE, HOIST_KV, _HoistedKV, _KVGradHolder, _LT_AUTOTUNE, _LT_ENABLED, _LT_PLANS,
     _LT_PLAN_BUDGET, _LT_RUN, _LT_UNSUPPORTED, _Linear, _LinearPacked, _PackedParam, _SPLITK_ENABLED, _SPLITK_MAX,

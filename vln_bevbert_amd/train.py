@@ -16,13 +16,14 @@ simply contribute zeros (the semantics of find_unused_parameters=True without th
 each step is drawn from a generator seeded identically on every rank, so the reference's per-step task-id broadcast
 (pretrain_src/data/loader.py:56-59) needs no collective at all.
 """
+import contextlib
 import os
 import random
 
 import torch
 import torch.distributed as dist
 
-from . import ops
+from . import capture, ops
 from .static_step import GraphedStep, StaticBatch
 
 
@@ -555,83 +556,64 @@ class PretrainTrainer:
             a.upload_flags()
             gs.graph.replay()
             return gs.loss.clone()
-        branches = ops.Branches.enabled
         if sb.eager_runs < self.GRAPH_WARMUP:
-            # the warm-up runs use the stream layout of the capture: the order in which the deferred weight-gradient work
-            # is issued (and with it the scratch addresses in the cached reduction task tables) depends on it
             sb.eager_runs += 1
-            ops.Branches.enabled = branches or self.graph_branches
-            try:
+            with self._capture_stream_layout():
                 loss = self._forward_backward(task, sb)
-            finally:
-                ops.Branches.enabled = branches
             self.optimizer_step(lr=None, fused_norm=True)
             return loss
         # capture: flags / plans / side streams are warm, nothing below allocates outside the graph's pool
         a.upload_flags()
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        if self._graph_pool is None:
-            # all step graphs of a trainer share one private memory pool: they are replayed one at a time on one stream
-            # and exchange nothing through pool memory, so the pool is as large as the largest step, not the sum
-            self._graph_pool = torch.cuda.graph_pool_handle()
-        ops.Branches.enabled = branches or self.graph_branches
-        # thread-local capture mode: other threads of the process keep making HIP calls while this one captures -- the
-        # loader's producer thread allocates pinned staging buffers and device buffer sets (loader.BucketManager), and
-        # ProcessGroupNCCL's watchdog polls the completion events of earlier eager collectives; in "global" mode any such
-        # call invalidates the capture (hipErrorStreamCaptureInvalidated; seen in round 4 with the first pin_memory() of a
-        # buffer set).  Calls made by THIS thread and by autograd's backward thread on its behalf are still checked.
-        mode = "thread_local"
         if self.reducer.active:
-            # the device is idle (synchronize above): give the watchdog one polling period to retire the eager works;
+            # with the device idle, give ProcessGroupNCCL's watchdog one polling period to retire the eager works;
             # collectives issued DURING capture are not handed to it
             import time
+            torch.cuda.synchronize()
             time.sleep(0.3)
-        err = None
+
+        def body():
+            # offsets restart; the salt word is read by the kernels at replay; the keep-bit generation of every attention
+            # site is captured as a side branch of the graph (ops.ATTN_BITS)
+            ops.RT.new_step(0, write_salt=False, plan_key=self._plan_key(task, sb))
+            loss = self._forward_backward(task, sb)
+            a.clip_and_step(None, self.betas, 1e-6, self.wd, self.grad_norm, grad_pre_scale=1.0 / self.world,
+                            fused_norm=True)
+            return loss
         try:
-            with torch.cuda.graph(graph, pool=self._graph_pool, capture_error_mode=mode):
-                try:
-                    # offsets restart; the salt word is read by the kernels at replay; the keep-bit generation of every
-                    # attention site is captured as a side branch of the graph (ops.ATTN_BITS)
-                    ops.RT.new_step(0, write_salt=False, plan_key=self._plan_key(task, sb))
-                    loss = self._forward_backward(task, sb)
-                    a.clip_and_step(None, self.betas, 1e-6, self.wd, self.grad_norm, grad_pre_scale=1.0 / self.world,
-                                    fused_norm=True)
-                except Exception as e:      # noqa: BLE001 -- still inside the capture: join the forked side streams so that
-                    err = e                 # the capture can END (an unjoined capture stays open on this ROCm, see ops)
-                    ops.join_captured_side_streams(extra=[self.reducer.stream])
-        except Exception as e:      # noqa: BLE001 -- ending the capture failed as well
-            err = err or e
-        if err is not None:
+            # all step graphs of a trainer share one private memory pool: they are replayed one at a time on one stream
+            # and exchange nothing through pool memory, so the pool is as large as the largest step, not the sum
+            with self._capture_stream_layout():
+                graph, loss = capture.capture(body, self._graph_pool, [self.reducer.stream])
+        except capture.CaptureFailed as e:
             # a step that cannot be captured (e.g. a collective library that refuses stream capture) is not fatal: nothing
-            # has executed, the trainer says so loudly and goes on eagerly
-            e = err
+            # has executed, the trainer says so loudly, forgets the capture's collective work handles and goes on eagerly
             import warnings
-            self.graph_error = f"{type(e).__name__}: {e}"[:400]
+            self.graph_error = e.message
             self.use_graphs = False
             warnings.warn(f"hipGraph capture of the {task} step failed, continuing with eager steps: {self.graph_error}")
-            ops.Branches.enabled = branches
-            from . import lib
-            lib.load().bevbert_hip_error_reset()     # the capture's error code must not surface in the next launch check
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("the failed hipGraph capture could not be ended: the stream is still capturing and the "
-                                   f"process cannot issue work any more ({self.graph_error})") from e
-            torch.cuda.synchronize()
-            # host state the aborted capture left behind points into its dead memory pool: deferred weight-gradient
-            # closures, queued reduction records, collective work handles -- forget them, the step is redone eagerly
-            ops.WgradStream.drop_pending()
-            ops.ReduceQueue.drop_pending()
             self.reducer.drop_pending()
             ops.RT.new_step(self._step_seed(), plan_key=self._plan_key(task, sb))
             loss = self._forward_backward(task, sb)
             self.optimizer_step(lr=None, fused_norm=True)
             return loss
-        ops.Branches.enabled = branches
+        self._graph_pool = graph.pool()
         gs = GraphedStep(graph, loss)
         gs.owner = self
         sb.graph = gs
         graph.replay()                              # the capture recorded the step; this replay executes it
         return loss.clone()
+
+    @contextlib.contextmanager
+    def _capture_stream_layout(self):
+        """The stream layout of a captured step (``graph_branches``), for the capture and for the warm-up runs before it: the
+        order in which the deferred weight-gradient work is issued -- and with it the scratch addresses in the cached
+        reduction task tables -- depends on it."""
+        branches = ops.Branches.enabled
+        ops.Branches.enabled = branches or self.graph_branches
+        try:
+            yield
+        finally:
+            ops.Branches.enabled = branches
 
 
 # ---------------------------------------------------------------------------------------------------------------
