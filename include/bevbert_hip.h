@@ -567,6 +567,50 @@ int bevbert_nav_metrics(const double* dist, int N, int S, const int* scan, const
                         double* items, double* avg, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Object grounding of the REVERIE / SOON fine-tune rollout (since 0.4.0; entry points added, ABI otherwise unchanged;
+ * csrc/nav_obj.hip).  Replaces map_nav_src/reverie/agent_obj.py:343-349 (_nav_obj_variable), :384-400 (_teacher_object),
+ * :516-526 (the 'og' record of node_stop_scores), :597-604 (pred_objid) and reverie/env.py:360-411 (_eval_item,
+ * eval_metrics).  Fixed shapes, lengths read on the device, no atomics, no entry synchronises with the host: every launch
+ * can sit inside a captured step. */
+
+/* Object rows of a panorama: obj (B,Op,H) dtype 0/1 with obj[b, j] = pano[b, view_len[b] + j] (pano (B,L,H)) for
+ * j < obj_len[b] and 0 otherwise; mask (B,Op) u8 = j < obj_len[b].  view_len, obj_len (B) i64.  H % 4 == 0.  Lengths are
+ * clamped to view_len in [0, L], obj_len in [0, min(Op, L - view_len)], so no value addresses outside the tensors.
+ * bwd is the adjoint in store form: EVERY row of dpano (B,L,H) is written, dobj[b, l - view_len[b]] inside the object
+ * segment and 0 elsewhere (no prior zero fill).  Both are pure copies. */
+int bevbert_obj_rows_fwd(const void* pano, const int64_t* view_len, const int64_t* obj_len, void* obj, uint8_t* mask, int B,
+                         int L, int Op, int H, int dtype, hipStream_t stream);
+int bevbert_obj_rows_bwd(const void* dobj, const int64_t* view_len, const int64_t* obj_len, void* dpano, int B, int L,
+                         int Op, int H, int dtype, hipStream_t stream);
+
+/* Object supervision and record of one navigation step; launch BEFORE bevbert_nav_action (it reads the pre-action ended).
+ * obj_logits (B,O) dtype 0/1 (-inf = masked), obj_ids (B,O) i32 (the caller's integer ids), obj_len (B) i64 (clamped to
+ * [0, O]), gt_obj (B), cur (B) node, end_vps (B,E) + n_end (B): the goal-viewpoint set, ended (B) u8.
+ * targets (B) i64 = -100 when ended or cur is not in end_vps[b, :n_end[b]], else the first j < obj_len[b] with
+ * obj_ids[b, j] == gt_obj[b] (-100 when there is none).  og_slot (B) i32 = torch.argmax of obj_logits[b, :obj_len[b]] (the
+ * first maximum; a NaN beats every number, the first NaN wins), -1 when obj_len[b] == 0.  For samples that are not ended
+ * stop_og[b, cur[b]] (B,N) i32 = og_slot >= 0 ? obj_ids[b, og_slot] : -1 (a revisit overwrites; cur outside [0, N) is
+ * not recorded). */
+int bevbert_nav_obj_step(const void* obj_logits, int dtype, int B, int O, const int* obj_ids, const int64_t* obj_len,
+                         const int* gt_obj, const int* cur, const int* end_vps, const int* n_end, int E, const uint8_t* ended,
+                         int* stop_og, int N, int64_t* targets, int* og_slot, hipStream_t stream);
+
+/* After bevbert_nav_action: for just_ended[b], pred_obj[b] = stop_node[b] in [0, N) ? stop_og[b, stop_node[b]] : -1; the
+ * other rows of pred_obj (B) i32 keep what they hold. */
+int bevbert_nav_obj_pick(const uint8_t* just_ended, const int* stop_node, const int* stop_og, int N, int* pred_obj, int B,
+                         hipStream_t stream);
+
+/* reverie/env.py _eval_item of B finished trajectories, f64; path / gt / action_steps as in bevbert_nav_metrics (no bound
+ * on Lp), goal_vps (B,E) + n_goal (B) the goal-viewpoint set, pred_obj / gt_obj (B) i32.  items (B,8): action_steps,
+ * trajectory_steps, trajectory_lengths, success (last path node in the goal set), oracle_success (any), spl, rgs
+ * (pred_obj == gt_obj), rgspl.  avg (8) or NULL: eval_metrics' means in the same order, the last five x100, summed in
+ * sample order.  Path lengths are summed by the routine bevbert_nav_metrics uses.  A scan outside [0, S): a row of NaN. */
+int bevbert_nav_metrics_obj(const double* dist, int N, int S, const int* scan, const int* path, const int* path_len, int Lp,
+                            const int* action_steps, const int* gt, const int* gt_len, int Lg, const int* goal_vps,
+                            const int* n_goal, int E, const int* pred_obj, const int* gt_obj, int B, double* items,
+                            double* avg, hipStream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Candidate waypoint prediction of the continuous-environment agent (since 0.2.0; entry points added, ABI otherwise
  * unchanged).  Replaces bevbert_ce/vlnce_baselines/waypoint_pred/transformer/waypoint_bert.py:66-86 (the ring-masked
  * self-attention of BinaryDistPredictor_TRM), models/Policy_ViewSelection_BEV.py:196-321 (mode 'waypoint' after the

@@ -23,14 +23,56 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from vln_bevbert_amd import nav_expert as NE  # noqa: E402
 from vln_bevbert_amd import ops, synthetic  # noqa: E402
 from vln_bevbert_amd.config import BevBertConfig  # noqa: E402
 from vln_bevbert_amd.feature_store import GridFeatureStore  # noqa: E402
 from vln_bevbert_amd.graph_map import GraphMapBatch  # noqa: E402
 from vln_bevbert_amd.graph_map_dev import DeviceGraphMap  # noqa: E402
 from vln_bevbert_amd.nav_model import VLNBert  # noqa: E402
-from vln_bevbert_amd.nav_static import NavGraphRunner, NavTrainRunner  # noqa: E402
+from vln_bevbert_amd.nav_static import NavGraphRunner, NavTrainRunner, nav_obj_variable  # noqa: E402
 from vln_bevbert_amd.pretrain_cmt import bevpos_polar  # noqa: E402
+from vln_bevbert_amd.static_step import OBJ_PAD  # noqa: E402
+
+
+def _node(vp):
+    """Node index of a synthetic viewpoint id 'e<i>_v<n>' (what ScanGraphs.index is to a real scan)."""
+    return -1 if vp is None else int(vp.rsplit("_v", 1)[1])
+
+
+def obj_episode_tensors(obs_all, ended_all, pano, cfg, n_nodes, g, dev):
+    """--objects: what a REVERIE agent uploads besides the R2R inputs.  Per step the panorama batches gain their object
+    tokens (agent_obj.py:70-140: obj_img_fts, loc_fts / nav_types over [views | objects], obj_lens) and the supervision its
+    per-sample ids (object ids, current node, ended flags); per episode the target object and its goal-viewpoint set."""
+    B = len(obs_all[0])
+    i32 = torch.int32
+    steps = []
+    for t, (obs, p) in enumerate(zip(obs_all, pano)):
+        lens = [len(ob["obj_ids"]) for ob in obs]
+        O = max(1, max(lens))
+        ids = torch.full((B, -(-O // OBJ_PAD) * OBJ_PAD), -1, dtype=i32)        # the width nav_obj_variable pads the logits to
+        nav_types = torch.cat([p["nav_types"].cpu(), torch.zeros(B, O, dtype=torch.long)], 1)
+        for i, ob in enumerate(obs):
+            ids[i, :lens[i]] = torch.tensor(ob["obj_ids"], dtype=i32)
+            nav_types[i, 36:36 + lens[i]] = 2
+        ang = torch.rand(B, O, 2, generator=g) * 6.28
+        loc = torch.cat([ang[..., :1].sin(), ang[..., :1].cos(), ang[..., 1:].sin(), ang[..., 1:].cos(),
+                         torch.rand(B, O, 3, generator=g)], -1)
+        p.update(obj_img_fts=torch.randn(B, O, cfg.obj_feat_size, generator=g).to(dev),
+                 loc_fts=torch.cat([p["loc_fts"], loc.to(dev)], 1), nav_types=nav_types.to(dev),
+                 obj_lens=torch.tensor(lens, dtype=torch.long, device=dev))
+        steps.append({"obj_ids": ids.to(dev), "obj_lens_host": lens, "view_lens_host": [36] * B,
+                      "cur": torch.tensor([_node(ob["viewpoint"]) for ob in obs], dtype=i32, device=dev),
+                      "ended": torch.from_numpy(ended_all[t].astype(np.uint8)).to(dev),
+                      # the navigation target of a live sample is [stop] (always a valid slot of the fused logits)
+                      "nav_targets": torch.from_numpy(np.where(ended_all[t], -100, 0).astype(np.int64)).to(dev)})
+    ends = [[_node(v) for v in ob["gt_end_vps"]] for ob in obs_all[0]]
+    E = max(map(len, ends))
+    return {"steps": steps, "n_nodes": n_nodes,
+            "gt_obj": torch.tensor([ob["gt_obj_id"] for ob in obs_all[0]], dtype=i32, device=dev),
+            "goal": torch.tensor([e[0] for e in ends], dtype=i32, device=dev),
+            "end_vps": torch.tensor([e + [-1] * (E - len(e)) for e in ends], dtype=i32, device=dev),
+            "n_end": torch.tensor(list(map(len, ends)), dtype=i32, device=dev)}
 
 
 def main():
@@ -56,10 +98,15 @@ def main():
                     help="size-independent properties of the rollout instead of timing (tests/test_gpu_model.py): every step's "
                          "fused logits are finite or -inf, every live sample has a finite best action, a second rollout "
                          "with the same step seed reproduces the logits")
+    ap.add_argument("--objects", type=int, default=0,
+                    help="N > 0: REVERIE-style episodes (BevBertConfig.reverie(), 0..N object tokens per panorama) through the "
+                         "full per-step chain of map_nav_src/reverie/agent_obj.py: panorama -> map -> nav_obj_variable -> "
+                         "navigation -> object_step -> action_step -> object_pick -> losses (nav_expert.il_loss on the "
+                         "fused and the object logits); 0: the R2R rollout")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     cdt = torch.bfloat16 if a.dtype == "bf16" else torch.float32
-    cfg = BevBertConfig()
+    cfg = BevBertConfig.reverie() if a.objects > 0 else BevBertConfig()
     torch.manual_seed(0)
     model = VLNBert(cfg)
     arena = model.vln_bert.finalize(dev, cdt)
@@ -74,7 +121,7 @@ def main():
     store = GridFeatureStore(keys, torch.randn(N, 12, 196, cfg.grid_feat_size, generator=g).half(),
                              torch.rand(N, 12, 14, 14, generator=g) * 0.6,
                              torch.randint(0, 40, (N, 12, 14, 14), generator=g).to(torch.uint8), dev)
-    obs_all, ended_all = synthetic.make_nav_episodes(B, T, seed=1, n_nodes=a.nodes)
+    obs_all, ended_all = synthetic.make_nav_episodes(B, T, seed=1, n_nodes=a.nodes, **({"objects": a.objects} if a.objects else {}))
     # instructions and per-step panorama features (36 views: candidates first, agent.py:70-112)
     txt_ids = torch.randint(1000, 2000, (B, 80), generator=g).to(dev)
     txt_masks = torch.ones(B, 80, dtype=torch.bool, device=dev)
@@ -90,6 +137,7 @@ def main():
         pano.append({"view_img_fts": torch.randn(B, 36, cfg.image_feat_size, generator=g).to(dev), "obj_img_fts": None,
                      "loc_fts": loc.to(dev), "nav_types": nav_types.to(dev),
                      "view_lens": torch.full((B,), 36, dtype=torch.long, device=dev), "obj_lens": None})
+    og = obj_episode_tensors(obs_all, ended_all, pano, cfg, a.nodes, g, dev) if a.objects > 0 else None
     pix, polar = ops.pixel_scale(cfg.grid_hw, dev), bevpos_polar(cfg.bev_dim, dev)
     t_book = [0.0]
     # infer: captured forward steps (nav_static.NavGraphRunner); train: forward + backward graphs per step of the episode
@@ -100,6 +148,7 @@ def main():
         a.warmup = max(a.warmup, runner.eager_uses + 1)      # eager episodes + the capture episode stay out of the timed region
 
     trace = []
+    trace_obj = []
 
     on_device = a.map == "device"
     actions = []
@@ -114,6 +163,13 @@ def main():
             gm.update_graph(obs_all[0])
         txt = model("language", {"txt_ids": txt_ids, "txt_masks": txt_masks})
         loss = 0.0
+        if og is not None:       # the episode's node_stop_scores ('stop' / 'og') and pred_objid, on the device
+            Nn = og["n_nodes"]
+            rec = {"stop_scores": torch.zeros(B, Nn, dtype=torch.float32, device=dev),
+                   "stop_order": torch.full((B, Nn), -1, dtype=torch.int32, device=dev),
+                   "n_stop": torch.zeros(B, dtype=torch.int32, device=dev),
+                   "stop_og": torch.full((B, Nn), -1, dtype=torch.int32, device=dev),
+                   "pred_obj": torch.full((B,), -1, dtype=torch.int32, device=dev)}
         for t in range(T):
             obs, ended = obs_all[t], ended_all[t]
             h0 = time.perf_counter()
@@ -146,14 +202,33 @@ def main():
                 "bev_masks": torch.ones(B, K, dtype=torch.bool, device=dev), "bev_nav_masks": bi["bev_nav_masks"],
                 "bev_cand_idxs": bi["bev_cand_idxs"], "bev_cand_vpids": bi["bev_cand_vpids"], "obj_embeds": None,
                 "obj_masks": None})
+            if og is not None:
+                st = og["steps"][t]
+                nav.update(nav_obj_variable(pe, pano[t]["view_lens"], pano[t]["obj_lens"],
+                                            view_lens_host=st["view_lens_host"], obj_lens_host=st["obj_lens_host"]))
             out = runner.navigation(nav) if use_graphs[0] else model("navigation", nav)
+            if og is not None:
+                # agent_obj.py:516-604 on the device: the 'og' record and the grounding target, the action, pred_objid
+                sup = NE.object_step(out["obj_logits"], st["obj_ids"], pano[t]["obj_lens"], og["gt_obj"], st["cur"],
+                                     og["end_vps"], og["n_end"], st["ended"], rec["stop_og"])
+                cand = torch.tensor([[_node(v) for v in vps] + [-1] * (out["fused_logits"].shape[1] - len(vps))
+                                     for vps in nav["gmap_vpids"]], dtype=torch.int32).to(dev, non_blocking=True)
+                act = NE.action_step(out["fused_logits"].detach(), "teacher" if a.mode == "train" else "argmax", t, T,
+                                     targets=st["nav_targets"], cand=cand, cur=st["cur"], goal=og["goal"],
+                                     ended=st["ended"].clone(), stop_scores=rec["stop_scores"],
+                                     stop_order=rec["stop_order"], n_stop=rec["n_stop"], seed=t)
+                NE.object_pick(act["just_ended"], act["stop_node"], rec["stop_og"], rec["pred_obj"])
+                if a.check:
+                    trace_obj.append(out["obj_logits"].float().clone())
+                if a.mode == "train":
+                    loss = loss + NE.il_loss(out["fused_logits"], st["nav_targets"]) + NE.il_loss(out["obj_logits"], sup["targets"])
             if a.feedback:      # agent.py:520-560: the action is picked on the host from the logits of THIS step
                 probs = torch.softmax(out["fused_logits"].float(), 1)
                 a_t = probs.argmax(1).cpu().numpy()                     # device -> host: the step's synchronisation point
                 actions.append([nav["gmap_vpids"][i][int(k)] for i, k in enumerate(a_t)])
             if a.check:
                 trace.append(out["fused_logits"].float().clone())
-            if a.mode == "train":       # teacher action: [stop] is always a valid target of the fused logits
+            if a.mode == "train" and og is None:       # teacher action: [stop] is always a valid target of the fused logits
                 live = torch.from_numpy(~ended).to(dev)
                 tgt = torch.zeros(B, dtype=torch.long, device=dev)
                 loss = loss + (F.cross_entropy(out["fused_logits"].float(), tgt, reduction="none") * live).sum()
@@ -210,11 +285,15 @@ def main():
         g0, g1 = got["eager"][0], got["graphs"][0]
         same = bool(torch.equal(g0, g1))
         rel = float((g0.double() - g1.double()).norm() / g0.double().norm().clamp_min(1e-30))
-        print(json.dumps({"check": "ok" if (same and got["graphs"][3] > 0 and got["graphs"][4] is None) else "FAILED",
-                          "mode": "train", "batch": B, "steps": T, "dtype": a.dtype, "gradients_bitwise_equal": same,
-                          "gradient_rel_l2_diff": rel, "loss_eager": got["eager"][1], "loss_graphs": got["graphs"][1],
-                          "captured_graphs": got["graphs"][3], "runner": got["graphs"][2], "graph_error": got["graphs"][4],
-                          "grad_norm": float(g0.double().norm())}))
+        rec = {"check": "ok" if (same and got["graphs"][3] > 0 and got["graphs"][4] is None) else "FAILED",
+               "mode": "train", "batch": B, "steps": T, "dtype": a.dtype, "gradients_bitwise_equal": same,
+               "gradient_rel_l2_diff": rel, "loss_eager": got["eager"][1], "loss_graphs": got["graphs"][1],
+               "captured_graphs": got["graphs"][3], "runner": got["graphs"][2], "graph_error": got["graphs"][4],
+               "grad_norm": float(g0.double().norm())}
+        if og is not None:       # the grounding loss reached its head (the arena still holds the graph arm's gradients)
+            rec.update(objects=a.objects, og_head_grad_norm=float(torch.sqrt(sum(
+                (p.main_grad.double() ** 2).sum() for p in model.vln_bert.og_head.parameters()))))
+        print(json.dumps(rec))
         return
     if a.check:
         runs = []
@@ -241,6 +320,7 @@ def main():
                 iteration(7)
             torch.cuda.synchronize()
             graphed = [t.cpu() for t in trace]
+            graphed_obj = [t.cpu() for t in trace_obj[-T:]]
             assert runner.graph_error is None, runner.graph_error
             assert runner.captured_graphs() >= 2 and runner.stats["replays"] > 0, runner.stats
             use_graphs[0] = False
@@ -262,6 +342,12 @@ def main():
                 flip = (~same).nonzero().flatten().tolist()
                 for i in flip:
                     assert abs(float(y[i].max() - y[i, x[i].argmax()])) <= tol * max(1.0, float(y[i][fin[i]].abs().max())), (t, i)
+            for t, (x, y) in enumerate(zip(graphed_obj, [t.cpu() for t in trace_obj[-T:]])):
+                # the object logits of the same steps: the padded object slots are cut off, the -inf pattern is the caller's
+                fin = torch.isfinite(y)
+                assert x.shape == y.shape and torch.equal(torch.isfinite(x), fin) and not torch.isnan(x).any(), t
+                if fin.any():
+                    worst = max(worst, float((x[fin] - y[fin]).abs().max()) / max(1.0, float(y[fin].abs().max())))
             assert worst <= tol, worst
             rec.update({"graphs_vs_eager_max_rel_diff": round(worst, 5), "captured_graphs": runner.captured_graphs(),
                         "runner": runner.stats})
@@ -286,7 +372,8 @@ def main():
             chk.nav_gmap_variable(obs)
             chk.bev_inputs(obs, store, pc_order=1, bev_dim=cfg.bev_dim, bev_res=cfg.bev_res)
         overflow = chk.check_overflow()
-    print(json.dumps({"workload": f"R2R fine-tune rollout, {a.mode}, batch {B}, {T} navigation steps, {a.dtype}, "
+    kind = "R2R" if og is None else f"REVERIE-style (0..{a.objects} object tokens per panorama, object grounding on the device)"
+    print(json.dumps({"workload": f"{kind} fine-tune rollout, {a.mode}, batch {B}, {T} navigation steps, {a.dtype}, "
                                   f"{'DeviceGraphMap (maps on the device)' if on_device else 'GraphMapBatch (host numpy)'} + "
                                   f"resident grid-feature store ({store.nbytes() / 2 ** 30:.1f} GiB)",
                       "action_feedback": "logits read back and argmaxed on the host every step (agent.py:520-560)"

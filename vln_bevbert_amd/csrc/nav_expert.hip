@@ -8,16 +8,11 @@
 // Node ids are scan indices in [0, N); any id outside that range reads as an unreachable node (distance inf).
 // Every f64 distance sum is formed in the reference's order, so DTW values and spl keys are bit-equal to numpy's; the
 // exp() of nDTW / CLS comes from the device math library.  No atomics: every reduction has a fixed order.
-#include "common.h"
+#include "nav_common.h"
 
-#define NE_INF __builtin_inf()
 #define NE_IGNORE (-100)
 #define NE_MAX_P 1024      // DTW rows (prediction length + 1) per wave: one LDS column of f64 + the node sequence
 #define NE_WAVES 4
-
-__device__ __forceinline__ double ne_d(const double* __restrict__ d, int N, int u, int v) {
-  return ((unsigned)u < (unsigned)N && (unsigned)v < (unsigned)N) ? d[(size_t)u * N + v] : NE_INF;
-}
 
 // cal_dtw's table (eval_utils.py:6-14) by one wave: lanes over the reference index in blocks of 64, anti-diagonal
 // steps.  At step k lane l computes D[i][j] with i = k - l, j = j0 + l + 1, from its own previous value (up), lane
@@ -430,9 +425,7 @@ __global__ __launch_bounds__(64) void ne_metrics_kernel(const double* __restrict
   }
   const double nav_error = ne_d(d, N, p[P - 1], goal);
   const double oracle_error = ne_d(d, N, near, goal);
-  double tlen = 0.0, glen = 0.0;
-  for (int i = 0; i + 1 < P; ++i) tlen += ne_d(d, N, p[i], p[i + 1]);
-  for (int i = 0; i + 1 < G; ++i) glen += ne_d(d, N, g[i], g[i + 1]);
+  const double tlen = ne_path_length(d, N, p, P), glen = ne_path_length(d, N, g, G);
   const double success = nav_error < margin ? 1.0 : 0.0;
   const double spl = success * glen / fmax(fmax(tlen, glen), 0.01);
   const double ndtw = exp(-dtw / (margin * G));

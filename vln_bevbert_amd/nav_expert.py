@@ -14,6 +14,13 @@ r2r/eval_utils.py ``cal_dtw`` / ``cal_cls``), with one ``.item()`` device sync p
     traj_append         bevbert_nav_traj_append FloydGraph.path of the agent map appended to the trajectory, scan indices
     nav_metrics         bevbert_nav_metrics     every field of _eval_item (fp64) + the eval_metrics batch means
 
+Object grounding of the REVERIE / SOON agent (map_nav_src/reverie/agent_obj.py:384-400,516-526,597-604; reverie/env.py:360-411;
+csrc/nav_obj.hip):
+
+    object_step         bevbert_nav_obj_step    _teacher_object targets, torch.argmax's slot, the per-node 'og' record
+    object_pick         bevbert_nav_obj_pick    traj[i]['pred_objid'] of the samples that just ended
+    nav_metrics_obj     bevbert_nav_metrics_obj success by goal-viewpoint set, spl, rgs, rgspl (fp64) + eval_metrics' means
+
 No call here reads anything back to the host: the caller decides when to copy the chosen nodes.
 """
 import json
@@ -373,3 +380,93 @@ def metrics_dicts(items, avg):
     per = {k: [int(v) if k in INT_FIELDS else float(v) for v in it[:, i]] for i, k in enumerate(METRIC_FIELDS)}
     av = avg.cpu().numpy()
     return {k: float(av[i]) for i, (k, _, _) in enumerate(AVG_FIELDS)}, per
+
+
+# ---------------------------------------------------------------------- object grounding (REVERIE / SOON), csrc/nav_obj.hip
+# per-item metric columns of bevbert_nav_metrics_obj, in the order reverie/env.py:_eval_item fills `scores`
+METRIC_FIELDS_OBJ = ("action_steps", "trajectory_steps", "trajectory_lengths", "success", "oracle_success", "spl", "rgs",
+                     "rgspl")
+# reverie/env.py eval_metrics' averaged dict: key -> (per-item column, scale)
+AVG_FIELDS_OBJ = (("action_steps", "action_steps", 1.0), ("steps", "trajectory_steps", 1.0),
+                  ("lengths", "trajectory_lengths", 1.0), ("sr", "success", 100.0), ("oracle_sr", "oracle_success", 100.0),
+                  ("spl", "spl", 100.0), ("rgs", "rgs", 100.0), ("rgspl", "rgspl", 100.0))
+
+
+def object_step(obj_logits, obj_ids, obj_lens, gt_obj, cur, end_vps, n_end, ended, stop_og, outs=None):
+    """`_teacher_object` and the 'og' record of one navigation step (reverie/agent_obj.py:384-400, 516-526) for B samples;
+    call it BEFORE action_step of the same step (it reads the pre-action `ended`).
+
+    obj_logits (B,O) fp32 / bf16 with -inf on masked slots; obj_ids (B,O) i32 the caller's integer object ids; obj_lens (B);
+    gt_obj (B) i32; cur (B) i32 current node; end_vps (B,E) i32 + n_end (B) i32 the gt_end_vps set; ended (B) u8;
+    stop_og (B,N) i32, indexed like stop_scores, is updated in place: a live sample records the id of its arg-max object
+    (-1 = None: no objects) under its current node, a revisit overwrites.
+
+    Returns a dict of device tensors: targets (B,) int64 for ``il_loss(obj_logits, targets)`` (IGNOREID when ended, off
+    the goal set, or the target is not among the objects), og_slot (B,) i32 = torch.argmax of the valid slots (-1: none)."""
+    B, O = obj_logits.shape
+    dev = obj_logits.device
+    if dev.type != "cuda" or obj_logits.dtype not in (torch.float32, torch.bfloat16):
+        raise lib.BevBertHipError("object_step: fp32 / bf16 device logits only")
+    i32, u8 = torch.int32, torch.uint8
+    N = _inout(stop_og, i32, dev, (B, stop_og.shape[1]), "stop_og").shape[1]
+    E = torch.as_tensor(end_vps).shape[1]
+    obj_ids, end_vps = _in(obj_ids, i32, dev, (B, O), "obj_ids"), _in(end_vps, i32, dev, (B, E), "end_vps")
+    obj_lens = _in(obj_lens, torch.int64, dev, (B,), "obj_lens")
+    gt_obj, cur, n_end = (_in(x, i32, dev, (B,), n) for x, n in ((gt_obj, "gt_obj"), (cur, "cur"), (n_end, "n_end")))
+    ended = _in(ended, u8, dev, (B,), "ended")
+    if outs is not None:
+        _inout(outs["targets"], torch.int64, dev, (B,), "targets")
+        _inout(outs["og_slot"], i32, dev, (B,), "og_slot")
+    else:
+        outs = {"targets": torch.empty(B, dtype=torch.int64, device=dev), "og_slot": torch.empty(B, dtype=i32, device=dev)}
+    call("bevbert_nav_obj_step", ptr(obj_logits.contiguous()), lib.dtype_code(obj_logits), B, O, ptr(obj_ids), ptr(obj_lens),
+         ptr(gt_obj), ptr(cur), ptr(end_vps), ptr(n_end), E, ptr(ended), ptr(stop_og), N, ptr(outs["targets"]),
+         ptr(outs["og_slot"]), stream())
+    return outs
+
+
+def object_pick(just_ended, stop_node, stop_og, pred_obj):
+    """traj[i]['pred_objid'] of the samples that stop this step (reverie/agent_obj.py:597-604); call it AFTER action_step
+    with its just_ended / stop_node (B,).  pred_obj (B,) i32 is persistent and updated in place: a just-ended sample gets
+    the 'og' record of its stop node (-1 = None), the other rows keep their value.  Returns pred_obj."""
+    dev = _device(pred_obj, stop_og)
+    B = pred_obj.shape[0]
+    N = _inout(stop_og, torch.int32, dev, (B, stop_og.shape[1]), "stop_og").shape[1]
+    _inout(pred_obj, torch.int32, dev, (B,), "pred_obj")
+    just_ended = _in(just_ended, torch.uint8, dev, (B,), "just_ended")
+    stop_node = _in(stop_node, torch.int32, dev, (B,), "stop_node")
+    call("bevbert_nav_obj_pick", ptr(just_ended), ptr(stop_node), ptr(stop_og), N, ptr(pred_obj), B, stream())
+    return pred_obj
+
+
+def nav_metrics_obj(graphs, scan, path, path_len, action_steps, gt, gt_len, goal_vps, n_goal, pred_obj, gt_obj):
+    """reverie/env.py `_eval_item` of B finished trajectories + eval_metrics' averages, in fp64 on the device.
+
+    scan, path (B,Lp), path_len, action_steps, gt (B,Lg), gt_len as in nav_metrics; goal_vps (B,E) i32 + n_goal (B) i32 the
+    viewpoints the target object is visible from (scan indices); pred_obj / gt_obj (B) i32 (-1 = no prediction).
+    Returns (items (B, 8) f64 in METRIC_FIELDS_OBJ order, avg (8,) f64 in AVG_FIELDS_OBJ order)."""
+    dev = _device(scan, path, gt, path_len)
+    dist, _ = graphs.to(dev)
+    B = torch.as_tensor(scan).shape[0]
+    Lp, Lg, E = (torch.as_tensor(x).shape[1] for x in (path, gt, goal_vps))
+    i32 = torch.int32
+    scan, path_len, action_steps, gt_len, n_goal, pred_obj, gt_obj = (_in(x, i32, dev, (B,), n) for x, n in (
+        (scan, "scan"), (path_len, "path_len"), (action_steps, "action_steps"), (gt_len, "gt_len"), (n_goal, "n_goal"),
+        (pred_obj, "pred_obj"), (gt_obj, "gt_obj")))
+    path, gt, goal_vps = _in(path, i32, dev, (B, Lp), "path"), _in(gt, i32, dev, (B, Lg), "gt"), \
+        _in(goal_vps, i32, dev, (B, E), "goal_vps")
+    items = torch.empty(B, len(METRIC_FIELDS_OBJ), dtype=torch.float64, device=dev)
+    avg = torch.empty(len(AVG_FIELDS_OBJ), dtype=torch.float64, device=dev)
+    call("bevbert_nav_metrics_obj", ptr(dist), graphs.n_max, len(graphs.scans), ptr(scan), ptr(path), ptr(path_len), Lp,
+         ptr(action_steps), ptr(gt), ptr(gt_len), Lg, ptr(goal_vps), ptr(n_goal), E, ptr(pred_obj), ptr(gt_obj), B,
+         ptr(items), ptr(avg), stream())
+    return items, avg
+
+
+def metrics_dicts_obj(items, avg):
+    """(averaged dict, per-item dict of lists) in reverie/env.py eval_metrics' format from nav_metrics_obj's tensors."""
+    it = items.cpu().numpy()
+    per = {k: [int(v) if k in INT_FIELDS else (bool(v) if k == "rgs" else float(v)) for v in it[:, i]]
+           for i, k in enumerate(METRIC_FIELDS_OBJ)}
+    av = avg.cpu().numpy()
+    return {k: float(av[i]) for i, (k, _, _) in enumerate(AVG_FIELDS_OBJ)}, per

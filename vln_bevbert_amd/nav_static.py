@@ -16,12 +16,20 @@ What stays on the host is what is host data anyway: the viewpoint-id lists of th
 table built from them (``sap_fusion_indices``); they are copied into the static buffers with the rest of the step's
 inputs.  A bucket is run eagerly twice (library GEMM plans are chosen by timing on first use) and captured on its third
 use.  Outputs are views of static buffers: they are valid until the next call of the same mode.
+
+Object tokens (REVERIE / SOON, map_nav_src/reverie/agent_obj.py): the object axis is one more padded axis.  Panorama:
+``obj_img_fts`` is padded to ``Op`` = a multiple of ``o_step`` objects and ``loc_fts`` / ``nav_types`` to V + Op tokens
+(padding tokens lie beyond view_lens + obj_lens: masked like the reference's in-batch padding), the outputs are sliced back
+to the caller's token axis.  Navigation: ``obj_embeds`` / ``obj_masks`` (``nav_obj_variable``) are padded to Op (mask
+False, zero rows) and ``obj_logits`` comes back sliced to the caller's width.  Both keys gain Op; a batch without objects
+builds the feeds, keys and outputs it always has.
 """
 import numpy as np
 import torch
 
 from . import capture
 from .graph_map import HostFeed
+from .ops_rowops import nav_obj_variable  # noqa: F401  (the rollout's _nav_obj_variable, next to the runners that consume it)
 from .pretrain_cmt import fuse_sap_logits, sap_fusion_indices
 
 
@@ -34,17 +42,27 @@ class _Bucket:
         self.inputs, self.outputs, self.graph, self.uses = inputs, None, None, 0
 
 
-def _slice_outputs(out, G, C):
-    """The navigation outputs without the padding of the node / candidate axes."""
+def _slice_outputs(out, G, C, O=None):
+    """The navigation outputs without the padding of the node / candidate (/ object: ``O``) axes."""
     return {"gmap_embeds": out["gmap_embeds"][:, :G], "global_logits": out["global_logits"][:, :G],
-            "local_logits": out["local_logits"][:, :C], "fused_logits": out["fused_logits"][:, :G], "obj_logits": None}
+            "local_logits": out["local_logits"][:, :C], "fused_logits": out["fused_logits"][:, :G],
+            "obj_logits": None if O is None else out["obj_logits"][:, :O]}
+
+
+def _obj_width(nav):
+    """The caller's object axis of a navigation step, None for a step without object tokens."""
+    return None if nav.get("obj_embeds") is None else nav["obj_embeds"].shape[1]
 
 
 class NavGraphRunner:
-    def __init__(self, model, g_step=8, c_step=8, eager_uses=2):
-        """``model``: nav_model.VLNBert in eval mode, parameters already in the arena."""
+    def __init__(self, model, g_step=8, c_step=8, eager_uses=2, o_step=None):
+        """``model``: nav_model.VLNBert in eval mode, parameters already in the arena.  ``o_step``: the object axis is padded
+        to a multiple of it (default: static_step.OBJ_PAD, the pad of the pre-training loader)."""
         self.model, self.net = model, model.vln_bert
         self.g_step, self.c_step, self.eager_uses = g_step, c_step, eager_uses
+        if o_step is None:
+            from .static_step import OBJ_PAD as o_step
+        self.o_step = int(o_step)
         self.buckets = {}
         self.stats = {"replays": 0, "eager": 0, "captures": 0}
         self.graph_error = None
@@ -93,28 +111,41 @@ class NavGraphRunner:
 
     # ------------------------------------------------------------------------------------------------ panorama
     def panorama(self, batch):
-        """``model('panorama', batch)`` for batches without object tokens; returns (pano_embeds, pano_masks)."""
-        if batch.get("obj_img_fts") is not None:
-            with torch.no_grad():
-                return self.model("panorama", batch)
-        feeds = {k: batch[k] for k in ("view_img_fts", "loc_fts", "nav_types", "view_lens")}
-        key = ("panorama",) + tuple(feeds["view_img_fts"].shape)
+        """``model('panorama', batch)``; returns (pano_embeds, pano_masks), with object tokens sliced to the batch's own
+        token axis."""
+        feeds, shapes, key, L = self._panorama_call(batch)
 
         def fn(x):
-            return self.net.forward_panorama_per_step(x["view_img_fts"], None, x["loc_fts"], x["nav_types"],
-                                                      x["view_lens"], None)
-        return self._run(key, feeds, fn)
+            return self.net.forward_panorama_per_step(x["view_img_fts"], x.get("obj_img_fts"), x["loc_fts"], x["nav_types"],
+                                                      x["view_lens"], x.get("obj_lens"))
+        pe, pm = self._run(("panorama",) + key, feeds, fn, shapes)
+        return (pe, pm) if L is None else (pe[:, :L], pm[:, :L])
+
+    def _panorama_call(self, batch):
+        """What a panorama step feeds its static buffers: (feeds, padded buffer shapes, shape-bucket key, L) -- L is the
+        token axis to slice the outputs back to, None for a batch without object tokens (nothing is padded then)."""
+        feeds = {k: batch[k] for k in ("view_img_fts", "loc_fts", "nav_types", "view_lens")}
+        key = tuple(feeds["view_img_fts"].shape)
+        if batch.get("obj_img_fts") is None:
+            return feeds, {}, key, None
+        B, V = key[:2]
+        O, L = batch["obj_img_fts"].shape[1], batch["loc_fts"].shape[1]
+        Op = _pad_to(O, self.o_step)
+        Lp = max(L, V + Op)
+        feeds.update(obj_img_fts=batch["obj_img_fts"], obj_lens=batch["obj_lens"])
+        shapes = {"obj_img_fts": (B, Op, batch["obj_img_fts"].shape[2]), "loc_fts": (B, Lp, batch["loc_fts"].shape[2]),
+                  "nav_types": (B, Lp)}
+        return feeds, shapes, key + (Op,), L
 
     # ------------------------------------------------------------------------------------------------ navigation
     def navigation(self, nav):
-        """``model('navigation', nav)`` (no object tokens).  ``nav`` is the dict the agent builds: the outputs of
-        ``GraphMapBatch.nav_gmap_variable`` / ``bev_inputs`` plus txt_embeds, txt_masks, bev_fts, bev_pos_fts."""
-        if nav.get("obj_embeds") is not None:
-            with torch.no_grad():
-                return self.model("navigation", nav)
+        """``model('navigation', nav)``.  ``nav`` is the dict the agent builds: the outputs of
+        ``GraphMapBatch.nav_gmap_variable`` / ``bev_inputs`` plus txt_embeds, txt_masks, bev_fts, bev_pos_fts and, with object
+        tokens, ``nav_obj_variable``'s obj_embeds / obj_masks."""
         feeds, shapes, key, (G, C) = self._navigation_call(nav, with_text=False)
         static = self._text_inputs(nav["txt_embeds"], nav["txt_masks"])
-        return _slice_outputs(self._run(("navigation",) + key, feeds, self._navigation_device, shapes, static), G, C)
+        return _slice_outputs(self._run(("navigation",) + key, feeds, self._navigation_device, shapes, static), G, C,
+                              _obj_width(nav))
 
     def _navigation_call(self, nav, with_text):
         """What a navigation step feeds its static buffers: (feeds, padded buffer shapes, shape-bucket key, (G, C)).  The
@@ -134,7 +165,14 @@ class NavGraphRunner:
         shapes = {"gmap_img_embeds": (B, Gp, nav["gmap_img_embeds"].shape[2]), "gmap_step_ids": (B, Gp),
                   "gmap_pos_fts": (B, Gp, nav["gmap_pos_fts"].shape[2]), "gmap_masks": (B, Gp),
                   "gmap_pair_dists": (B, Gp, Gp), "gmap_visited_masks": (B, Gp), "bev_cand_idxs": (B, Cp)}
-        return feeds, shapes, (B, Gp, Cp, nav["txt_embeds"].shape[1], nav["bev_fts"].shape[1]), (G, C)
+        key = (B, Gp, Cp, nav["txt_embeds"].shape[1], nav["bev_fts"].shape[1])
+        O = _obj_width(nav)
+        if O is not None:       # object tokens: one more padded axis, one more entry of the key
+            Op = _pad_to(O, self.o_step)
+            feeds.update(obj_embeds=nav["obj_embeds"], obj_masks=nav["obj_masks"])
+            shapes.update(obj_embeds=(B, Op, nav["obj_embeds"].shape[2]), obj_masks=(B, Op))
+            key += (Op,)
+        return feeds, shapes, key, (G, C)
 
     def _text_inputs(self, txt_embeds, txt_masks):
         """Static buffers of the instruction: its states and mask, and their K|V projections for every cross-attention
@@ -172,8 +210,9 @@ class NavGraphRunner:
         b_kvs = net.local_encoder.encoder.split_kv(x["b_kv"]) if "b_kv" in x else None
         gmap_embeds = net.global_encoder(x["txt_embeds"], x["txt_masks"], g_in, x["gmap_masks"], x["gmap_pair_dists"],
                                          txt_kvs=g_kvs)
-        bev_embeds, _ = net.local_encoder(x["txt_embeds"], x["txt_masks"], x["bev_fts"], x["bev_pos_fts"], None,
-                                          x["bev_nav_masks"], None, None, txt_kvs=b_kvs)
+        obj_in, obj_masks = (x["obj_embeds"].to(cd), x["obj_masks"]) if "obj_embeds" in x else (None, None)
+        bev_embeds, obj_embeds = net.local_encoder(x["txt_embeds"], x["txt_masks"], x["bev_fts"], x["bev_pos_fts"], None,
+                                                   x["bev_nav_masks"], obj_in, obj_masks, txt_kvs=b_kvs)
         if net.sap_fuse_linear is None:
             fuse_weights = 0.5
         else:
@@ -189,8 +228,11 @@ class NavGraphRunner:
         local_logits = net.local_sap_head(cand_embeds).squeeze(2).float() * (1 - fuse_weights)
         local_logits = local_logits.masked_fill(cand_masks.logical_not(), -float("inf"))
         fused_logits = fuse_sap_logits(global_logits, local_logits, x["src"], x["vis_c"])
-        return {"gmap_embeds": gmap_embeds, "global_logits": global_logits, "local_logits": local_logits,
-                "fused_logits": fused_logits}
+        out = {"gmap_embeds": gmap_embeds, "global_logits": global_logits, "local_logits": local_logits,
+               "fused_logits": fused_logits}
+        if obj_embeds is not None:                                      # map_nav_src/models/vilmodel.py:873-877
+            out["obj_logits"] = net.og_head(obj_embeds).squeeze(2).float().masked_fill(obj_masks.logical_not(), -float("inf"))
+        return out
 
     def captured_graphs(self):
         return sum(b.graph is not None for b in self.buckets.values())
@@ -276,8 +318,8 @@ class NavTrainRunner(NavGraphRunner):
     """``panorama`` / ``navigation`` of a TRAINING rollout (see the block comment above).  ``begin_episode()`` before each
     rollout; ``end_capture()`` after the forward of the capture episode (``capturing`` says when that is)."""
 
-    def __init__(self, model, arena, g_step=8, c_step=8, eager_uses=2, graphs=True):
-        super().__init__(model, g_step=g_step, c_step=c_step, eager_uses=eager_uses)
+    def __init__(self, model, arena, g_step=8, c_step=8, eager_uses=2, graphs=True, o_step=None):
+        super().__init__(model, g_step=g_step, c_step=c_step, eager_uses=eager_uses, o_step=o_step)
         self.arena, self.graphs = arena, graphs
         self.segs, self.episode, self.capturing = {}, 0, False
         self._order, self._t = [], {"panorama": 0, "navigation": 0}
@@ -404,24 +446,25 @@ class NavTrainRunner(NavGraphRunner):
 
     # ---- the two modes
     def panorama(self, batch):
-        if batch.get("obj_img_fts") is not None:
-            return self.model("panorama", batch)
-        feeds = {k: batch[k] for k in ("view_img_fts", "loc_fts", "nav_types", "view_lens")}
+        feeds, shapes, key, L = self._panorama_call(batch)
         model = self.model
 
         def fn(x):
-            pe, pm = model("panorama", {"view_img_fts": x["view_img_fts"], "obj_img_fts": None, "loc_fts": x["loc_fts"],
-                                        "nav_types": x["nav_types"], "view_lens": x["view_lens"], "obj_lens": None})
+            pe, pm = model("panorama", {"view_img_fts": x["view_img_fts"], "obj_img_fts": x.get("obj_img_fts"),
+                                        "loc_fts": x["loc_fts"], "nav_types": x["nav_types"], "view_lens": x["view_lens"],
+                                        "obj_lens": x.get("obj_lens")})
             return {"pano_embeds": pe, "pano_masks": pm}
-        out = self._segment("panorama", tuple(feeds["view_img_fts"].shape), feeds, (), fn, {}, ("pano_embeds", "pano_masks"))
-        return out["pano_embeds"], out["pano_masks"]
+        out = self._segment("panorama", key, feeds, (), fn, shapes, ("pano_embeds", "pano_masks"))
+        pe, pm = out["pano_embeds"], out["pano_masks"]
+        return (pe, pm) if L is None else (pe[:, :L], pm[:, :L])
 
     def navigation(self, nav):
-        if nav.get("obj_embeds") is not None:
-            return self.model("navigation", nav)
         feeds, shapes, key, (G, C) = self._navigation_call(nav, with_text=True)
-        feeds["gmap_img_embeds"] = feeds["gmap_img_embeds"].to(nav["txt_embeds"].dtype)
-        diff = tuple(k for k in ("txt_embeds", "gmap_img_embeds") if feeds[k].requires_grad)
+        O = _obj_width(nav)
+        for k in ("gmap_img_embeds",) + (("obj_embeds",) if O is not None else ()):
+            feeds[k] = feeds[k].to(nav["txt_embeds"].dtype)
+        diff = tuple(k for k in ("txt_embeds", "gmap_img_embeds") + (("obj_embeds",) if O is not None else ())
+                     if feeds[k].requires_grad)
         drop = self.model
 
         def fn(x):
@@ -430,8 +473,9 @@ class NavTrainRunner(NavGraphRunner):
             y["bev_fts"] = ops.dropout(x["bev_fts"], drop.feat_dropout, True)        # VLNBert.forward('navigation'), model.py:36
             return self._navigation_device(y)
         out = self._segment("navigation", key + (diff,), feeds, diff, fn, shapes,
-                            ("gmap_embeds", "global_logits", "local_logits", "fused_logits"))
-        return _slice_outputs(out, G, C)
+                            ("gmap_embeds", "global_logits", "local_logits", "fused_logits")
+                            + (("obj_logits",) if O is not None else ()))
+        return _slice_outputs(out, G, C, O)
 
     def captured_graphs(self):
         return sum((s.fwd is not None) + (s.bwd is not None) for s in self.segs.values())

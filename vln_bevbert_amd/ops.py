@@ -30,9 +30,9 @@ from .ops_gemm import (  # noqa: F401
     _tuning_loaded, _warn_fallback, _wgrad_into, gemm_plan_count, hoisted_kv, linear, linear_packed, linear_packed_res,
     linear_res, load_gemm_tuning_table, save_gemm_tuning_table)
 from .ops_rowops import (  # noqa: F401
-    SegmentCSR, _BiasDropResLN, _BiasDropResLN32, _BiasGelu, _CrossEntropy, _DropoutAdd, _EmbedLN, _SapLoss,
+    SegmentCSR, _BiasDropResLN, _BiasDropResLN32, _BiasGelu, _CrossEntropy, _DropoutAdd, _EmbedLN, _ObjRows, _SapLoss,
     _SegmentWsum, bev_bin_points, bev_lift_bin, bev_splat_mean, bias_dropout_residual_layernorm, bias_dropout_residual_prenorm, bias_gelu, bias_relu, take_rows, weighted_mean, bce_rows, sem_select, bias_layernorm_plus, smallk_linear_layernorm_plus, smallk_linear_layernorm_plus_supported,
-    cross_entropy_rows, dropout, dropout_keep_mask, embed_sum_layernorm, embedding_grad_small, layernorm, pixel_scale, sap_loss,
+    cross_entropy_rows, dropout, dropout_keep_mask, embed_sum_layernorm, embedding_grad_small, layernorm, nav_obj_variable, pixel_scale, sap_loss,
     sap_loss_supported, segment_wsum, soft_ce_rows)
 from .ops_attention import (  # noqa: F401
     _Attention, _strides, attention, attention_cross, attention_self, attn_drop_bits, graph_bias)

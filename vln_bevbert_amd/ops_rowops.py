@@ -641,6 +641,56 @@ def take_rows(x, idx, idx2=None):
     return _TakeRows.apply(x.contiguous(), idx, idx2)
 
 
+class _ObjRows(torch.autograd.Function):
+    """obj[b, j] = pano[b, view_lens[b] + j] for j < obj_lens[b], else 0, and the mask j < obj_lens[b]: one launch, the
+    lengths read on the device.  The backward stores the whole (B, L, H) gradient in one launch (bevbert_obj_rows_bwd)."""
+
+    @staticmethod
+    def forward(ctx, pano, view_lens, obj_lens, Op):
+        B, L, H = pano.shape
+        obj = torch.empty((B, Op, H), dtype=pano.dtype, device=pano.device)
+        mask = torch.empty((B, Op), dtype=torch.bool, device=pano.device)
+        call("bevbert_obj_rows_fwd", ptr(pano), ptr(view_lens), ptr(obj_lens), ptr(obj), ptr(mask), B, L, Op, H,
+             dtype_code(pano), stream())
+        ctx.save_for_backward(view_lens, obj_lens)
+        ctx.shape = (B, L, H)
+        ctx.mark_non_differentiable(mask)
+        return obj, mask
+
+    @staticmethod
+    def backward(ctx, dobj, _dmask):
+        view_lens, obj_lens = ctx.saved_tensors
+        B, L, H = ctx.shape
+        dobj = dobj.contiguous()
+        dpano = torch.empty(ctx.shape, dtype=dobj.dtype, device=dobj.device)
+        call("bevbert_obj_rows_bwd", ptr(dobj), ptr(view_lens), ptr(obj_lens), ptr(dpano), B, L, dobj.shape[1], H,
+             dtype_code(dobj), stream())
+        return dpano, None, None, None
+
+
+def nav_obj_variable(pano_embeds, view_lens, obj_lens, pad=None, view_lens_host=None, obj_lens_host=None):
+    """map_nav_src/reverie/agent_obj.py:343-349 (_nav_obj_variable): the object rows of every panorama, padded to one
+    width, and their mask -> {"obj_embeds" (B, Op, H), "obj_masks" (B, Op) bool}.  ``Op`` is the largest object count rounded
+    up to ``pad`` (default static_step.OBJ_PAD; no objects at all: one pad step); padding rows are zero and masked, as the
+    reference's in-batch padding.  The width is host knowledge: ``obj_lens_host`` / ``view_lens_host`` (lists; the agent
+    builds the lengths from its observations) spare the read-back of device length tensors.  Lengths that do not fit
+    (view_len + obj_len > L) are refused here; the kernel itself clamps them."""
+    from .static_step import OBJ_PAD
+    pad = OBJ_PAD if pad is None else int(pad)
+    B, L, H = pano_embeds.shape
+    if pad < 1 or H % 4 != 0 or pano_embeds.dtype not in (torch.float32, torch.bfloat16):
+        raise lib.BevBertHipError(f"nav_obj_variable: pad={pad}, H={H} (a multiple of 4), dtype {pano_embeds.dtype}")
+    host = lambda given, t: [int(x) for x in (given if given is not None else (t.tolist() if torch.is_tensor(t) else t))]
+    vl, ol = host(view_lens_host, view_lens), host(obj_lens_host, obj_lens)
+    if len(vl) != B or len(ol) != B or any(v < 0 or o < 0 or v + o > L for v, o in zip(vl, ol)):
+        raise lib.BevBertHipError(f"nav_obj_variable: view_lens {vl} + obj_lens {ol} do not fit {B} panoramas of {L} tokens")
+    Op = max(pad, (max(ol) + pad - 1) // pad * pad)
+    dev = pano_embeds.device
+    view_lens, obj_lens = (torch.as_tensor(x, device=dev).to(torch.int64).contiguous() for x in (view_lens, obj_lens))
+    obj, mask = _ObjRows.apply(pano_embeds.contiguous(), view_lens, obj_lens, Op)
+    return {"obj_embeds": obj, "obj_masks": mask}
+
+
 def bias_gelu(x, bias):
     """gelu_erf(x + bias) -- vilmodel.py:31-37,177-180."""
     return _BiasGelu.apply(x, bias)

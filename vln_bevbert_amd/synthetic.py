@@ -335,11 +335,16 @@ def gmap_csr(batch, device):
 
 
 # ----------------------------------------------------------------------------- fine-tune rollouts (graph bookkeeping)
-def make_nav_episodes(B, T, seed, n_nodes=14, degree=3):
+def make_nav_episodes(B, T, seed, n_nodes=14, degree=3, objects=0):
     """Synthetic observation streams for the fine-tune bookkeeping (map_nav_src/r2r/env.py _get_obs fields the agent's
     graph code reads): per episode a random connectivity graph of viewpoints with 3-D positions and a T-step walk that
     revisits nodes now and then.  Returns obs[t][i] = {'scan', 'viewpoint', 'position', 'heading', 'elevation',
-    'candidate': [{'viewpointId', 'position', 'pointId'}]} and ended[t] (B,) flags (episodes stop at random steps)."""
+    'candidate': [{'viewpointId', 'position', 'pointId'}]} and ended[t] (B,) flags (episodes stop at random steps).
+
+    ``objects`` > 0 adds the REVERIE fields (map_nav_src/reverie/env.py _get_obs): every viewpoint shows 0..objects objects
+    ('obj_ids', integer ids, the same list at every visit), the episode's target 'gt_obj_id' is one of the start viewpoint's
+    (which shows at least one) and 'gt_end_vps' lists the viewpoints that show it.  The walks and flags are those of
+    ``objects=0``: the object fields are drawn from a stream of their own."""
     rng = np.random.default_rng(seed)
     graphs = []
     for i in range(B):
@@ -353,6 +358,20 @@ def make_nav_episodes(B, T, seed, n_nodes=14, degree=3):
         graphs.append((pos, [sorted(s) for s in adj]))
     cur = [int(rng.integers(0, n_nodes)) for _ in range(B)]
     stop_at = [int(rng.integers(max(2, T - 2), T + 1)) for _ in range(B)]
+    obj_fields = None
+    if objects > 0:
+        orng = np.random.default_rng([seed, objects])
+        obj_fields = []
+        for i in range(B):
+            shown = [[int(o) for o in orng.choice(1000, size=int(orng.integers(0, objects + 1)), replace=False)]
+                     for _ in range(n_nodes)]
+            if not shown[cur[i]]:
+                shown[cur[i]] = [int(orng.integers(0, 1000))]
+            target = shown[cur[i]][int(orng.integers(len(shown[cur[i]])))]
+            for n in orng.choice(n_nodes, size=2, replace=False):      # the target is visible from a few more viewpoints
+                if target not in shown[n] and len(shown[n]) < objects:
+                    shown[n].append(target)
+            obj_fields.append((shown, target, [f"e{i}_v{n}" for n in range(n_nodes) if target in shown[n]]))
     obs, ended = [], []
     for t in range(T):
         step = []
@@ -365,6 +384,9 @@ def make_nav_episodes(B, T, seed, n_nodes=14, degree=3):
                 "candidate": [{"viewpointId": f"e{i}_v{n}", "position": tuple(float(x) for x in pos[n]),
                                "pointId": int(k)} for k, n in enumerate(adj[c])],
             })
+            if obj_fields is not None:
+                shown, target, end_vps = obj_fields[i]
+                step[-1].update(obj_ids=list(shown[c]), gt_obj_id=target, gt_end_vps=list(end_vps))
         obs.append(step)
         ended.append(np.asarray([t >= stop_at[i] for i in range(B)]))
         for i in range(B):
