@@ -20,11 +20,7 @@ import torch
 
 from . import lib
 from .lib import ptr, stream
-
-
-def call(name, *args):
-    from . import ops          # traced C-ABI call (bench.py's kernel-timing pass)
-    return ops.call(name, *args)
+from .ops_core import call          # the traced C-ABI call (bench.py's kernel-timing pass)
 
 CHUNK = 1024
 _ZERO_KERNEL = __import__("os").environ.get("BEVBERT_ZERO_KERNEL", "0") == "1"      # A/B: fill kernel instead of a memset command

@@ -11,17 +11,20 @@ every such problem is reported once through ``warnings`` (``ops.GEMM_FALLBACKS``
 Gradient sinks: a parameter that lives in a ParamArena (arena.py) carries ``main_grad`` (fp32 view of the flat
 gradient arena).  Backward kernels accumulate straight into that view and the Function returns ``None`` for the
 parameter, so there are no per-parameter AccumulateGrad kernels, no bucket copies for the all-reduce, and the
-optimiser sees one flat buffer.  Plain tensors (unit tests) get ordinary returned gradients.
+optimiser sees one flat buffer.  Plain tensors (unit tests) get ordinary returned gradients; a frozen parameter gets
+nothing.  ``ops_core.grad_dest`` / ``grad_dests`` is the one statement of that rule, and ``ops_reduce.colsum_launch``
+the one launcher of the two-stage column reductions (deferred to the step's single finalize launch, or in place).
 """
 from . import lib  # noqa: F401
 from .lib import call as _raw_call  # noqa: F401
 from .lib import dtype_code, ptr, stream  # noqa: F401
 from .ops_core import (  # noqa: F401
-    ATTN_BITS, Branches, HEAD_DIM, RT, RowOfTable, _AttnBitsPlanner, _DROP_BITS_WORDS,
+    ARENA, ATTN_BITS, Branches, HEAD_DIM, NONE, PLAIN, RT, RowOfTable, _AttnBitsPlanner, _DROP_BITS_WORDS,
     _LT_WS_BYTES, _Runtime, _UseParam, _compute, _drop_bits_words, _f32, _gemm, _hash32,
-    _mark_touched, _sink, call, use_param)
+    _mark_touched, _sink, call, grad_dest, grad_dests, grad_kind, params_in_arena, use_param)
 from .ops_reduce import (  # noqa: F401
-    ReduceQueue, SCRATCH, ScratchRing, WgradStream, _PARTIAL_ROWS, _on_launch_stream, _partial_rows)
+    ReduceQueue, SCRATCH, ScratchRing, WgradStream, _PARTIAL_ROWS, _on_launch_stream, _partial_rows, colsum_launch,
+    defers_finalize)
 from .capture import join_captured_side_streams  # noqa: F401
 from .ops_gemm import (  # noqa: F401
     GEMM_FALLBACKS, GEMM_TUNING_FILE, HOIST_KV, _HoistedKV, _KVGradHolder, _LT_AUTOTUNE, _LT_ENABLED, _LT_PLANS,

@@ -5,7 +5,7 @@ import math
 import torch
 
 from .lib import dtype_code, load, ptr, stream
-from .ops_core import ATTN_BITS, HEAD_DIM, RT, _drop_bits_words, _mark_touched, _sink, call
+from .ops_core import ATTN_BITS, HEAD_DIM, RT, _drop_bits_words, call, grad_dests
 
 
 # ----------------------------------------------------------------------------- K2 attention
@@ -178,16 +178,7 @@ class _GraphBias(torch.autograd.Function):
         if h.buf is None and not extra:
             return None, None, None, None, None
         B, G = dists.shape[0], dists.shape[-1]
-        sinks, tmp = [], None
-        for i, p in enumerate((weight, bias)):
-            s = _sink(p) if p.requires_grad else None
-            if s is not None:
-                _mark_touched(p)
-            elif p.requires_grad:             # a plain parameter: reduced into a temporary, returned to autograd
-                if tmp is None:
-                    tmp = torch.zeros(2, dtype=torch.float32, device=dists.device)
-                s = tmp[i:i + 1]
-            sinks.append(s)
+        sinks, _, give = grad_dests((weight, bias), 1, dists.device, zero=True)      # the kernel adds to its destinations
         ws = torch.empty(1024, dtype=torch.float32, device=dists.device)
         if h.buf is not None:
             call("bevbert_graph_bias_bwd", ptr(h.buf), ptr(dists), h.layers, B, h.nh, G, ptr(sinks[0]), ptr(sinks[1]),
@@ -196,9 +187,7 @@ class _GraphBias(torch.autograd.Function):
             st = torch.stack([g.to(torch.float32) for g in extra])
             call("bevbert_graph_bias_bwd", ptr(st), ptr(dists), len(extra), B, 1, G, ptr(sinks[0]), ptr(sinks[1]),
                  ptr(ws), stream())
-        gw, gb = (None if tmp is None or _sink(p) is not None or not p.requires_grad else s.view(p.shape).to(p.dtype)
-                  for p, s in zip((weight, bias), sinks))
-        return None, gw, gb, None, None
+        return (None, *give(), None, None)
 
 
 def graph_bias(dists, weight, bias, layers, nh):

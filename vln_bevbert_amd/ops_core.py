@@ -282,9 +282,51 @@ def _sink(param):
 
 def _mark_touched(param):
     param = getattr(param, "table", param)          # RowOfTable: the parameter is the table
-    arena = getattr(param, "arena", None)
-    if arena is not None:
-        arena.touch(param)
+    for p in getattr(param, "params", (param,)):    # _PackedParam: every parameter of the run
+        arena = getattr(p, "arena", None)
+        if arena is not None:
+            arena.touch(p)
+
+
+# ----------------------------------------------------------------------------- where a parameter gradient goes
+# THE rule: every backward node that produces a parameter gradient resolves it here, once.
+NONE, ARENA, PLAIN = "none", "arena", "plain"
+
+
+def grad_kind(p):
+    if p is None or not p.requires_grad:
+        return NONE
+    return ARENA if _sink(p) is not None else PLAIN
+
+
+def grad_dest(p):
+    """(kind, sink) of a parameter-like object (nn.Parameter, RowOfTable, _PackedParam or None):
+    NONE   missing or frozen: no pointer, nothing touched, autograd gets None;
+    ARENA  the kernel accumulates into ``sink`` (p.main_grad); touched here and nowhere else; autograd gets None;
+    PLAIN  the caller makes a fresh fp32 tensor (accumulate 0) and returns it cast to p.dtype."""
+    kind = grad_kind(p)
+    if kind == ARENA:
+        _mark_touched(p)
+    return kind, (_sink(p) if kind == ARENA else None)
+
+
+def grad_dests(params, n, device, zero=False):
+    """The up-to-three parameter outputs of ONE launch: (destination tensors, accumulate flag, ``give``).  The kernel takes
+    one flag, so arena and plain parameters do not mix.  ``give()`` is the tuple to return to autograd -- call it after the
+    launch.  ``n``: elements of a fresh fp32 destination (``zero``: the kernel adds to it)."""
+    kinds = [grad_kind(p) for p in params]
+    assert len(set(kinds) - {NONE}) <= 1, "mixed arena / plain parameters in one launch"
+    make = torch.zeros if zero else torch.empty
+    dests = [grad_dest(p)[1] if k == ARENA else make(n, dtype=torch.float32, device=device) if k == PLAIN else None
+             for p, k in zip(params, kinds)]
+    give = lambda: tuple(d.view(p.shape).to(p.dtype) if k == PLAIN else None for p, k, d in zip(params, kinds, dests))
+    return dests, int(ARENA in kinds), give
+
+
+def params_in_arena(params):
+    """Every parameter is an fp32 master that is frozen or lives in a ParamArena: what the kernels that write parameter
+    gradients straight into their sinks (small-K projection, graph bias) ask of their callers."""
+    return all(p.dtype == torch.float32 and grad_kind(p) != PLAIN for p in params)
 
 
 class RowOfTable:
@@ -330,13 +372,10 @@ class _UseParam(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        p = ctx.p
-        sink = _sink(p)
-        if sink is None:
-            return g
-        _mark_touched(p)
-        sink.add_(g.to(sink.dtype))
-        return None
+        kind, sink = grad_dest(ctx.p)
+        if kind == ARENA:
+            sink.add_(g.to(sink.dtype))
+        return g if kind == PLAIN else None
 
 
 def use_param(p):

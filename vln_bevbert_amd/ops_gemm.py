@@ -8,8 +8,8 @@ import torch.nn.functional as F
 
 from . import lib
 from .lib import dtype_code, ptr, stream
-from .ops_core import RT, _LT_WS_BYTES, _compute, _gemm, _mark_touched, _sink, call
-from .ops_reduce import ReduceQueue, WgradStream, _on_launch_stream, _partial_rows
+from .ops_core import ARENA, NONE, PLAIN, RT, _LT_WS_BYTES, _compute, _gemm, call, grad_dest
+from .ops_reduce import ReduceQueue, WgradStream, _on_launch_stream, colsum_launch
 
 
 # Library GEMMs go straight to hipBLASLt through the C ABI (bevbert_gemm): ~7 us of host time per call instead of the
@@ -242,15 +242,14 @@ def _param_grads(w_sink, b_sink, dyc, xc):
         if part is not None and lib._override is not None:
             WgradStream._keep.append(part)
     if b_sink is not None:
-        C = dyc.shape[1]
-        if WgradStream.DEFER_FINALIZE and dyc.shape[0] > 0:
-            nb = _partial_rows(dyc.shape[0])
-            part = RT.scratch.alloc(nb * C * 4, dyc.device)
-            call("bevbert_colsum_partials", ptr(dyc), part, dyc.shape[0], C, dtype_code(dyc), stream())
-            ReduceQueue.add(part, nb, 1, C, (ptr(b_sink), None, None))
-        else:
-            ws = RT.workspace(dyc.device, lib.load().bevbert_colsum_workspace_floats(C))
-            call("bevbert_colsum", ptr(dyc), ptr(b_sink), ptr(ws), dyc.shape[0], C, dtype_code(dyc), 1, stream())
+        _colsum(dyc, b_sink, 1)
+
+
+def _colsum(dyc, out, accumulate):
+    """out (fp32, C) (+)= column sums of dyc (rows x C, C a multiple of 4)."""
+    rows, C = dyc.shape
+    colsum_launch("bevbert_colsum", (ptr(dyc),), (out,), (rows, C, dtype_code(dyc)), accumulate, (), rows, C, dyc.device,
+                  first_stage="bevbert_colsum_partials")
 
 
 # ----------------------------------------------------------------------------- library GEMM with arena wgrad
@@ -279,38 +278,24 @@ class _Linear(torch.autograd.Function):
         x2 = x.reshape(-1, x.shape[-1])
         M, N, K = dy2.shape[0], dy2.shape[1], x2.shape[1]
         dx = _gemm("dgrad", lambda: _linear_dgrad(dy2, w_c, dres), M, K, N).view(x.shape) if ctx.needs_input_grad[0] else None
-        gw = gb = None
-        w_sink = _sink(weight) if weight.requires_grad else None
-        b_sink = _sink(bias) if (bias is not None and bias.requires_grad) else None
-        C = dy2.shape[1]
-        if weight.requires_grad and w_sink is None:
-            gw = _linear_wgrad(dy2, x2).to(weight.dtype)
-        if bias is not None and bias.requires_grad and (b_sink is None or C % 4 != 0):
-            if C % 4 != 0:                                  # the 1-wide heads, the 30 522-wide vocabulary bias
-                dyc = dy2 if dy2.is_contiguous() else dy2.contiguous()
-                if b_sink is not None and dyc.is_cuda:
-                    _mark_touched(bias)
-                    call("bevbert_colsum_any", ptr(dyc), ptr(b_sink), dyc.shape[0], C, dtype_code(dyc), 1, stream())
-                    b_sink = None
-                elif b_sink is not None:
-                    _mark_touched(bias)
-                    b_sink.add_(dy2.float().sum(0))
-                    b_sink = None
-                else:
-                    gb = dy2.float().sum(0).to(bias.dtype)
+        (wk, w_sink), (bk, b_sink) = grad_dest(weight), grad_dest(bias)
+        gw = _linear_wgrad(dy2, x2).to(weight.dtype) if wk == PLAIN else None
+        gb = None
+        dyc = dy2.contiguous() if (bk != NONE or w_sink is not None) else dy2
+        if bk == PLAIN and N % 4 != 0:
+            gb = dy2.float().sum(0).to(bias.dtype)
+        elif bk == PLAIN:
+            t = torch.empty(N, dtype=torch.float32, device=dy.device)
+            _colsum(dyc, t, 0)
+            gb = t.to(bias.dtype)
+        elif bk == ARENA and N % 4 != 0:                    # the 1- and 3-wide heads, the 30 522-wide vocabulary bias: in line
+            if dyc.is_cuda:
+                call("bevbert_colsum_any", ptr(dyc), ptr(b_sink), M, N, dtype_code(dyc), 1, stream())
             else:
-                ws = RT.workspace(dy.device, lib.load().bevbert_colsum_workspace_floats(C))
-                dyc = dy2 if dy2.is_contiguous() else dy2.contiguous()
-                t = torch.empty(C, dtype=torch.float32, device=dy.device)
-                call("bevbert_colsum", ptr(dyc), ptr(t), ptr(ws), dyc.shape[0], C, dtype_code(dyc), 0, stream())
-                gb = t.to(bias.dtype)
+                b_sink.add_(dy2.float().sum(0))
+            b_sink = None
         if w_sink is not None or b_sink is not None:        # arena parameters: accumulate on the weight-gradient stream
-            dyc = dy2 if dy2.is_contiguous() else dy2.contiguous()
-            xc = x2 if x2.is_contiguous() else x2.contiguous()
-            if w_sink is not None:
-                _mark_touched(weight)
-            if b_sink is not None:
-                _mark_touched(bias)
+            xc = x2.contiguous()
             WgradStream.submit(dy.device, lambda: _param_grads(w_sink, b_sink, dyc, xc), dyc, xc, dy)
         return dx, gw, gb, None, None, None
 
@@ -342,10 +327,6 @@ class _PackedParam:
         self.dtype = params[0].dtype
         self.arena = getattr(params[0], "arena", None)
 
-    def touch(self):
-        for p in self.params:
-            _mark_touched(p)
-
 
 class _LinearPacked(torch.autograd.Function):
     @staticmethod
@@ -367,13 +348,10 @@ class _LinearPacked(torch.autograd.Function):
         x2 = x.reshape(-1, x.shape[-1])
         M, N, K = dy2.shape[0], dy2.shape[1], x2.shape[1]
         dx = _gemm("dgrad", lambda: _linear_dgrad(dy2, pw.compute, dres), M, K, N).view(x.shape) if ctx.needs_input_grad[0] else None
-        if pw.requires_grad:
-            pw.touch()
-            pb.touch()
-            C = dy2.shape[1]
-            dyc = dy2 if dy2.is_contiguous() else dy2.contiguous()
-            xc = x2 if x2.is_contiguous() else x2.contiguous()
-            WgradStream.submit(dy.device, lambda: _param_grads(pw.main_grad, pb.main_grad, dyc, xc), dyc, xc, dy)
+        w_sink, b_sink = grad_dest(pw)[1], grad_dest(pb)[1]
+        if w_sink is not None or b_sink is not None:
+            dyc, xc = dy2.contiguous(), x2.contiguous()
+            WgradStream.submit(dy.device, lambda: _param_grads(w_sink, b_sink, dyc, xc), dyc, xc, dy)
         return dx, None, None, None
 
 
@@ -445,11 +423,10 @@ class _HoistedKV(torch.autograd.Function):
         x2 = x.reshape(-1, x.shape[-1])
         M, N, K = dy2.shape[0], dy2.shape[1], x2.shape[1]
         dx = _gemm("dgrad", lambda: _linear_dgrad(dy2, pw.compute), M, K, N).view(x.shape) if ctx.needs_input_grad[0] else None
-        if pw.requires_grad:
-            pw.touch()
-            pb.touch()
-            xc = x2 if x2.is_contiguous() else x2.contiguous()
-            WgradStream.submit(dy2.device, lambda: _param_grads(pw.main_grad, pb.main_grad, dy2, xc), dy2, xc, h.buf)
+        w_sink, b_sink = grad_dest(pw)[1], grad_dest(pb)[1]
+        if w_sink is not None or b_sink is not None:
+            xc = x2.contiguous()
+            WgradStream.submit(dy2.device, lambda: _param_grads(w_sink, b_sink, dy2, xc), dy2, xc, h.buf)
         return dx, None, None, None
 
 

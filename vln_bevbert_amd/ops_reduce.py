@@ -7,7 +7,7 @@ import os as _os
 import torch
 
 from . import lib
-from .lib import stream
+from .lib import ptr, stream
 from .ops_core import Branches, RT, call
 
 
@@ -478,6 +478,34 @@ class ReduceQueue:
             ent = cls._tables[key] = [cls._build(tuple(r), device) for r in rounds]
         for table, n in ent:
             call("bevbert_multi_finalize", table.data_ptr(), n, stream())
+
+
+def defers_finalize(accumulate, device, rows):
+    """THE deferral decision: a column sum into the arena, on a device, over at least one row, joins the step's one
+    bevbert_multi_finalize (BEVBERT_DEFER_FINALIZE=0: every second stage runs where its first stage does)."""
+    return accumulate == 1 and WgradStream.DEFER_FINALIZE and device.type == "cuda" and rows > 0
+
+
+def colsum_launch(entry, head, dests, mid, accumulate, tail, rows, C, device, first_stage=None):
+    """The one launcher of the two-stage column reductions (LayerNorm gamma / beta / bias, activation and projection biases):
+    entry(*head, *dests, workspace, *mid, accumulate, *tail, stream) with one or three ``dests`` of C columns each.
+    Deferred (``defers_finalize``): the kernel gets null destinations and leaves its per-block partial sums in the scratch
+    ring; the second stage joins the step's other pending reductions (ReduceQueue: one launch, off the critical path).
+    Otherwise both stages run here, through the stream's workspace.  ``first_stage``: an entry that is only the first
+    stage, first_stage(*head, partials, *mid, *tail, stream) -- it takes neither destinations nor the flag."""
+    nwhich = len(dests)
+    assert nwhich in (1, 3)
+    if defers_finalize(accumulate, device, rows):
+        nb = _partial_rows(rows)
+        part = RT.scratch.alloc(nb * nwhich * C * 4, device)
+        if first_stage is not None:
+            call(first_stage, *head, part, *mid, *tail, stream())
+        else:
+            call(entry, *head, *(None,) * nwhich, part, *mid, 1, *tail, stream())
+        ReduceQueue.add(part, nb, nwhich, C, tuple(ptr(d) for d in dests) + (None,) * (3 - nwhich))
+    else:
+        ws = RT.workspace(device, lib.load().bevbert_colsum_workspace_floats(nwhich * C))
+        call(entry, *head, *(ptr(d) for d in dests), ptr(ws), *mid, accumulate, *tail, stream())
 
 
 def _on_launch_stream(fn):

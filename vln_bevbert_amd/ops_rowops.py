@@ -8,8 +8,8 @@ import torch
 
 from . import lib
 from .lib import dtype_code, ptr, stream
-from .ops_core import RT, _compute, _f32, _mark_touched, _sink, call
-from .ops_reduce import ReduceQueue, WgradStream, _on_launch_stream, _partial_rows
+from .ops_core import ARENA, PLAIN, RT, RowOfTable, _compute, _f32, call, grad_dest, grad_dests, grad_kind, params_in_arena
+from .ops_reduce import ReduceQueue, WgradStream, colsum_launch
 
 
 def embedding_grad_small(ids, d, sink, table_rows):
@@ -27,44 +27,6 @@ def embedding_grad_small(ids, d, sink, table_rows):
 
 
 # ----------------------------------------------------------------------------- K3 LayerNorm family
-def _ln_param_dests(gamma, beta, bias, H, dev):
-    """Where the gamma / beta / bias column sums of a LayerNorm backward go: ((dgamma, dbeta, dbias) tensors handed to the
-    kernel, (gamma, beta, bias) fp32 results to return through autograd, accumulate flag).  A parameter in the gradient arena
-    is accumulated into its sink (flag 1, nothing returned), a plain tensor gets a fresh fp32 vector (flag 0), a missing
-    one or a frozen bias (e.g. fix_lang_embedding) nothing."""
-    outs = []
-    for p in (gamma, beta, bias):
-        if p is None:
-            outs.append((None, None, 0))
-        elif p is bias and not getattr(p, "requires_grad", True):
-            outs.append((None, None, None))
-        elif _sink(p) is not None:
-            outs.append((_sink(p), None, 1))
-            _mark_touched(p)
-        else:
-            t = torch.empty(H, dtype=torch.float32, device=dev)
-            outs.append((t, t, 0))
-    (dg, rg, ag), (db, rb, ab), (dbi, rbi, abi) = outs
-    assert ag == ab and (bias is None or abi is None or abi == ag), "mixed arena / plain parameters in one LayerNorm"
-    return (dg, db, dbi), (rg, rb, rbi), ag
-
-
-def _ln_bwd_call(entry, head, mid, tail, dests, accumulate, rows, H, dev, ws=None):
-    """entry(*head, dgamma, dbeta, dbias, workspace, *mid, accumulate, *tail, stream).  Arena parameters (accumulate 1):
-    the kernel leaves its per-block partial sums in the scratch ring and the second stage of the reduction joins the step's
-    other pending reductions (ReduceQueue: one launch, off the critical path); otherwise both stages run here, through
-    the stream's workspace (``ws``: the caller's, when it has taken it already)."""
-    if accumulate == 1 and WgradStream.DEFER_FINALIZE and dev.type == "cuda":
-        nb = _partial_rows(rows)
-        part = RT.scratch.alloc(nb * 3 * H * 4, dev)
-        call(entry, *head, None, None, None, part, *mid, 1, *tail, stream())
-        ReduceQueue.add(part, nb, 3, H, tuple(ptr(d) for d in dests))
-    else:
-        if ws is None:
-            ws = RT.workspace(dev, lib.load().bevbert_colsum_workspace_floats(3 * H))
-        call(entry, *head, *(ptr(d) for d in dests), ptr(ws), *mid, accumulate, *tail, stream())
-
-
 class _BiasDropResLN(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, bias, residual, gamma, beta, eps, drop_p, inplace_z, post1=None, post2=None, return_z=False):
@@ -121,22 +83,20 @@ class _BiasDropResLN(torch.autograd.Function):
         dz = torch.empty_like(dy)
         dx = torch.empty_like(dy) if (drop_p > 0 and has_res) else None
         dev = dy.device
-        ws = RT.workspace(dev, lib.load().bevbert_colsum_workspace_floats(3 * H))
-        (dg, db, dbi), (rg, rb, rbi), ag = _ln_param_dests(gamma, beta, bias, H, dev)
+        dests, acc, give = grad_dests((gamma, beta, bias), H, dev)
         # without a residual branch only dx is needed (it is the single input gradient)
         if not has_res and drop_p > 0:
             dx, dz_ptr = dz, None
         else:
             dz_ptr = dz
-        _ln_bwd_call("bevbert_layernorm_bwd_add", (ptr(dy), ptr(z), ptr(mean), ptr(rstd), ptr(_f32(gamma)), ptr(dz_ptr),
-                                                   ptr(dx), ptr(add)), (rows, H, dtype_code(dy), drop_p, seed, off), (),
-                     (dg, db, dbi), ag, rows, H, dev, ws)
+        colsum_launch("bevbert_layernorm_bwd_add", (ptr(dy), ptr(z), ptr(mean), ptr(rstd), ptr(_f32(gamma)), ptr(dz_ptr),
+                                                    ptr(dx), ptr(add)), dests, (rows, H, dtype_code(dy), drop_p, seed, off),
+                      acc, (), rows, H, dev)
         gx = dx if dx is not None else dz
         gres = dz if has_res else None
-        cast = lambda r, p: None if r is None else r.to(p.dtype)
         g1, g2 = (dy if has else None for has in ctx.posts)      # the post terms were added after the affine
-        return (gx, cast(rbi, bias) if bias is not None else None, gres, cast(rg, gamma), cast(rb, beta), None, None, None,
-                g1, g2, None)
+        rg, rb, rbi = give()
+        return gx, rbi, gres, rg, rb, None, None, None, g1, g2, None
 
 
 class _Res32Handle:
@@ -210,13 +170,12 @@ class _BiasDropResLN32(torch.autograd.Function):
         dy32 = dy32.contiguous() if dy32 is not None else None
         dz32 = torch.empty(z32.shape, dtype=res_dtype, device=dev)     # the residual's gradient, in the residual's dtype
         dx16 = torch.empty(z32.shape, dtype=torch.bfloat16, device=dev)
-        (dg, db, dbi), (rg, rb, rbi), ag = _ln_param_dests(gamma, beta, bias, H, dev)
-        _ln_bwd_call("bevbert_layernorm_res32_bwd", (ptr(dy16), ptr(dy32), ptr(z32), ptr(mean), ptr(rstd), ptr(_f32(gamma)),
-                                                     ptr(dz32), ptr(dx16)), (rows, H, drop_p, seed, off), (dtype_code(dz32),),
-                     (dg, db, dbi), ag, rows, H, dev)
-        cast = lambda r, p: None if r is None else r.to(p.dtype)
-        gres = dz32
-        return dx16, cast(rbi, bias) if bias is not None else None, gres, cast(rg, gamma), cast(rb, beta), None, None, None, None
+        dests, acc, give = grad_dests((gamma, beta, bias), H, dev)
+        colsum_launch("bevbert_layernorm_res32_bwd", (ptr(dy16), ptr(dy32), ptr(z32), ptr(mean), ptr(rstd), ptr(_f32(gamma)),
+                                                      ptr(dz32), ptr(dx16)), dests, (rows, H, drop_p, seed, off), acc,
+                      (dtype_code(dz32),), rows, H, dev)
+        rg, rb, rbi = give()
+        return dx16, rbi, dz32, rg, rb, None, None, None, None
 
 
 def bias_dropout_residual_layernorm(x, bias, residual, gamma, beta, eps, drop_p=0.0, training=False,
@@ -294,19 +253,14 @@ class _SmallKLinearLN(torch.autograd.Function):
         dy = dy.contiguous()
         K, H = feat.shape[-1], weight.shape[0]
         rows = feat.numel() // K
-        sinks = []
-        for p in (weight, bias, gamma, beta):
-            s = _sink(p) if (p is not None and p.requires_grad) else None
-            if s is not None:
-                _mark_touched(p)
-            sinks.append(s)
+        sinks = [grad_dest(p)[1] for p in (weight, bias, gamma, beta)]       # (params_in_arena: none of them is plain)
         ws = RT.scratch.alloc(int(lib.load().bevbert_smallk_workspace_floats(rows, K, H)) * 4, dy.device)
         call("bevbert_smallk_linear_layernorm_bwd", ptr(dy), ptr(feat), ptr(weight), ptr(bias), ptr(mean), ptr(rstd),
              ptr(_f32(gamma)), ptr(sinks[0]), ptr(sinks[1]), ptr(sinks[2]), ptr(sinks[3]), ws, rows, K, H, dtype_code(dy),
              stream())
-        if idx is not None and table.requires_grad:
-            _mark_touched(table)
-            embedding_grad_small(idx.reshape(-1), dy.reshape(-1, H), _sink(table), table.shape[0])
+        tsink = grad_dest(table if idx is not None else None)[1]
+        if tsink is not None:
+            embedding_grad_small(idx.reshape(-1), dy.reshape(-1, H), tsink, table.shape[0])
         return None, None, None, None, None, None, dy, None, None, None
 
 
@@ -316,7 +270,7 @@ def smallk_linear_layernorm_plus_supported(feat, lin, ln, post1, emb=None):
     H, K = lin.weight.shape
     ps = [lin.weight, lin.bias, ln.weight, ln.bias] + ([emb.weight] if emb is not None else [])
     return (feat.is_cuda and K <= 16 and H in (256, 512, 768, 1024) and (K + 8) * H * 4 + 512 <= 65536
-            and WgradStream.DEFER_FINALIZE and all(p.dtype == torch.float32 and (not p.requires_grad or _sink(p) is not None) for p in ps)
+            and WgradStream.DEFER_FINALIZE and params_in_arena(ps)
             and post1.dtype in (torch.float32, torch.bfloat16))
 
 
@@ -502,21 +456,10 @@ class _BiasGelu(torch.autograd.Function):
         rows = x.numel() // C
         dy = dy.contiguous()
         dx = torch.empty_like(dy)
-        ws = RT.workspace(dy.device, lib.load().bevbert_colsum_workspace_floats(C))
-        sink = _sink(bias)
-        if sink is not None:
-            _mark_touched(bias)
-            if WgradStream.DEFER_FINALIZE:      # second reduction stage batched with the step's others (see _BiasDropResLN)
-                nb = _partial_rows(rows)
-                part = RT.scratch.alloc(nb * C * 4, dy.device)
-                call(entry, ptr(dy), ptr(x), ptr(_f32(bias)), ptr(dx), None, part, rows, C, dtype_code(dy), 1, stream())
-                ReduceQueue.add(part, nb, 1, C, (ptr(sink), None, None))
-                return dx, None, None
-            call(entry, ptr(dy), ptr(x), ptr(_f32(bias)), ptr(dx), ptr(sink), ptr(ws), rows, C, dtype_code(dy), 1, stream())
-            return dx, None, None
-        db = torch.empty(C, dtype=torch.float32, device=dy.device)
-        call(entry, ptr(dy), ptr(x), ptr(_f32(bias)), ptr(dx), ptr(db), ptr(ws), rows, C, dtype_code(dy), 0, stream())
-        return dx, db.to(bias.dtype), None
+        dests, acc, give = grad_dests((bias,), C, dy.device)
+        colsum_launch(entry, (ptr(dy), ptr(x), ptr(_f32(bias)), ptr(dx)), dests, (rows, C, dtype_code(dy)), acc, (), rows, C,
+                      dy.device)
+        return dx, give()[0], None
 
 
 class _WeightedMean(torch.autograd.Function):
@@ -730,23 +673,13 @@ class _EmbedLN(torch.autograd.Function):
         rows = B * L
         dy = dy.contiguous()
         dz = torch.empty_like(dy)
-        ws = RT.workspace(dy.device, lib.load().bevbert_colsum_workspace_floats(3 * H))
-        sg, sb = _sink(gamma), _sink(beta)
-        assert (sg is None) == (sb is None)
         # the broadcast token-type row: its gradient is the column sum of dz = the kernel's third (dbias) output, through
-        # the deterministic two-stage reduction (a torch sum over the 5 120 rows would depend on the GPU's load)
-        styp = _sink(typ)[type_index] if (sg is not None and typ.requires_grad and _sink(typ) is not None) else None
-        if sg is not None:
-            _mark_touched(gamma); _mark_touched(beta)
-            if styp is not None:
-                _mark_touched(typ)
-            rg = rb = None
-        else:
-            rg = torch.empty(H, dtype=torch.float32, device=dy.device)
-            rb = torch.empty(H, dtype=torch.float32, device=dy.device)
-        _ln_bwd_call("bevbert_layernorm_bwd", (ptr(dy), ptr(z), ptr(mean), ptr(rstd), ptr(_f32(gamma)), ptr(dz), None),
-                     (rows, H, dtype_code(dy), 0.0, 0, 0), (), (sg, sb, styp) if sg is not None else (rg, rb, None),
-                     1 if sg is not None else 0, rows, H, dy.device, ws)
+        # the deterministic two-stage reduction (a torch sum over the 5 120 rows would depend on the GPU's load) -- unless
+        # gamma / beta are plain tensors, whose launch cannot also accumulate into the arena
+        row = RowOfTable(typ, type_index) if grad_kind(typ) == ARENA and grad_kind(gamma) != PLAIN else None
+        dests, acc, give = grad_dests((gamma, beta, row), H, dy.device)
+        colsum_launch("bevbert_layernorm_bwd", (ptr(dy), ptr(z), ptr(mean), ptr(rstd), ptr(_f32(gamma)), ptr(dz), None),
+                      dests, (rows, H, dtype_code(dy), 0.0, 0, 0), acc, (), rows, H, dy.device)
         dz2 = dz.reshape(rows, H)
         dzf = dz2          # (kept alive by the deferred closures below)
 
@@ -756,29 +689,27 @@ class _EmbedLN(torch.autograd.Function):
         def pos_grad(t):        # position p receives the sum over the batch: column sums of dz viewed as (B, L * H)
             call("bevbert_colsum_any", ptr(dz2), ptr(t), B, L * H, dtype_code(dz2), 1, stream())
 
-        def typ_grad(t):        # (only when the LayerNorm backward's third column sum could not take it, see styp)
+        def typ_grad(t):        # (only when the LayerNorm backward's third column sum could not take it, see ``row``)
             call("bevbert_colsum_any", ptr(dz2), ptr(t[type_index]), rows, H, dtype_code(dz2), 1, stream())
 
-        makers = ((word, word_grad), (pos, pos_grad), (typ, typ_grad))
+        makers = ((word, word_grad), (pos, pos_grad), (None if row is not None else typ, typ_grad))
         outs, deferred = [], []
         for p, make in makers:
-            if not p.requires_grad:
-                outs.append(None)
-            elif p is typ and styp is not None:
-                outs.append(None)              # written by the LayerNorm backward's column reduction above
-            elif _sink(p) is not None:
-                _mark_touched(p)
-                deferred.append((make, _sink(p)))
-                outs.append(None)
-            else:
+            kind, sink = grad_dest(p)
+            t = None
+            if kind == ARENA:
+                deferred.append((make, sink))
+            elif kind == PLAIN:
                 t = torch.zeros(p.shape, dtype=torch.float32, device=dy.device)
                 make(t)
-                outs.append(t.to(p.dtype))
+                t = t.to(p.dtype)
+            outs.append(t)
         if deferred:
             # every write into a parameter's gradient sink goes through the weight-gradient stream: the word table also
             # receives the tied MLM decoder's dW there (a deferred, non-atomic read-modify-write), the type table the
             # panorama branch's row-1 gradient -- one stream keeps the writers of a sink in program order
             WgradStream.submit(dy.device, lambda: [m(t) for m, t in deferred], dz2, dzf, ids, dy)
+        rg, rb, _ = give()
         return (None, outs[0], outs[1], outs[2], rg, rb, None, None, None, None, None, None)
 
 

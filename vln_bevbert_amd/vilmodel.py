@@ -555,7 +555,7 @@ class ImageEmbeddings(nn.Module):
             loc = _small_k_linear(loc_fts, self.loc_linear, cd)
             e = ops.bias_layernorm_plus(loc, self.loc_linear.bias, self.loc_layer_norm.weight, self.loc_layer_norm.bias, 1e-12,
                                         e, embedding_lookup(self.nav_type_embedding, nav_types))
-        if getattr(type_embed_layer.weight, "main_grad", None) is not None or not type_embed_layer.weight.requires_grad:
+        if ops.params_in_arena([type_embed_layer.weight]):
             # + token-type row 1 as the broadcast bias of the final LayerNorm (added in fp32 inside the kernel; its gradient
             # is the kernel's deterministic column reduction: ops.RowOfTable)
             e = ops.bias_dropout_residual_layernorm(e, ops.RowOfTable(type_embed_layer.weight, 1), None,
@@ -602,22 +602,20 @@ class _GatherRows(torch.autograd.Function):
     def backward(ctx, dy):
         (idx,) = ctx.saved_tensors
         table = ctx.table
-        if not table.requires_grad:
+        kind, sink = ops.grad_dest(table)
+        if kind == ops.NONE:
             return None, None, None
-        sink = ops._sink(table)
         d = dy.reshape(-1, dy.shape[-1])
-        if sink is not None and d.is_cuda and d.shape[1] % 4 == 0 and ops.WgradStream.DEFER_FINALIZE:
+        if d.shape[1] % 4 == 0 and ops.defers_finalize(kind == ops.ARENA, d.device, d.shape[0]):
             # the tables here have 2..100 rows and up to 28 224 gradient rows: per-(table row, row slice) sums without
             # atomics (index_add_ piles 0.3 ms of atomics onto two destination rows), folded into the arena by the
             # step's batched accumulate -- one launch here, none for the fold
-            ops._mark_touched(table)
             ops.embedding_grad_small(idx.reshape(-1), d.contiguous(), sink, table.shape[0])
             return None, None, None
         # fallback (CPU reference runs, no arena): a one-hot GEMM (rows x N) @ (N x H), deterministic as well
         onehot = F.one_hot(idx.reshape(-1), table.shape[0]).to(d.dtype)
         g = onehot.t().mm(d)
-        if sink is not None:
-            ops._mark_touched(table)
+        if kind == ops.ARENA:
             # sink writes live on the weight-gradient stream (the token-type table is also written by _EmbedLN there)
             ops.WgradStream.submit(dy.device, lambda: ops._on_launch_stream(lambda: sink.add_(g)), g, dy)
             return None, None, None
@@ -747,7 +745,7 @@ class GlobalMapEncoder(nn.Module):
         if self.sprel_linear is None:
             return None
         lw, lb = self.sprel_linear.weight, self.sprel_linear.bias
-        if gmap_pair_dists.is_cuda and all(p.dtype == torch.float32 and (not p.requires_grad or ops._sink(p) is not None) for p in (lw, lb)):
+        if gmap_pair_dists.is_cuda and ops.params_in_arena((lw, lb)):
             n_layers = self.encoder.num_x_layers
             nh = self.encoder.x_layers[0].visn_self_att.self.num_attention_heads
             return ops.graph_bias(gmap_pair_dists, lw, lb, n_layers, nh)
