@@ -15,7 +15,8 @@
  *   - return value 0 = ok, <0 = error (-1 invalid argument, -2 launch failure, -3 unsupported); the message is
  *     available from bevbert_last_error() (thread-local);
  *   - dtype codes: 0 = float32, 1 = bfloat16, 2 = float16; parameters (bias, gamma, beta) and statistics are always
- *     float32; arithmetic is float32 everywhere except the MFMA operands of the bf16 attention path;
+ *     float32; arithmetic is float32 everywhere except the MFMA operands of the bf16 attention path and of the float16
+ *     attention forward (bevbert_attn_f16_fwd); float16 is taken by that entry, the bevbert_vit_* row kernels and the GEMMs;
  *   - dropout masks are a pure function of (seed, offset, flat element index) -- a 32-bit site key from (seed, offset),
  *     16 random bits per element, two elements per 32-bit mix: backward entries regenerate the forward's mask from
  *     the same (seed, offset) instead of storing it.  Attention indexes its elements as
@@ -118,6 +119,15 @@ int bevbert_attn_drop_bits(uint64_t* drop_bits, int B, int nh, int Lq, int Lk, f
 /* 1: fill the workspace of this dropout site ahead of its forward (bevbert_attn_drop_bits, then bits_ready = 1); 0: pass
  * bits_ready = 0 -- the forward hashes inline and leaves the bits behind for the backward (small score matrices). */
 int bevbert_attn_bits_ahead(int Lq, int Lk, int has_bias);
+
+/* Float16 attention forward (since 0.5.0; entry point added, ABI otherwise unchanged; csrc/attn_f16.hip): the attention of
+ * the CLIP image encoder's float16 mode, inference only.  o = softmax(q k^T * scale) v with fp16 q / k / v / o (B, L, nh*64)
+ * and the stride block of bevbert_attn_fwd; no key mask, no bias, no dropout, no lse.  Any Lq, Lk >= 1, head_dim 64.
+ * Scores, maximum and row sum are fp32; P is rounded to fp16 (nearest even) for the P V product, which accumulates in
+ * fp32; the quotient by the row sum is rounded to fp16 once and overflows to inf as IEEE fp16 does.  Pointers 16-byte
+ * aligned, strides multiples of 8 elements.  bevbert_attn_fwd / _bwd / bevbert_attn_plan keep rejecting dtype 2. */
+int bevbert_attn_f16_fwd(const void* q, const void* k, const void* v, void* o, const int64_t* strides, int B, int nh, int Lq,
+                         int Lk, int head_dim, float scale, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * K3  y = LayerNorm(dropout(x + bias) + residual).
@@ -347,7 +357,8 @@ int bevbert_accum_partials(const void* partials, float* sink, int S, int64_t n, 
  *   C[M x N] = alpha * op(A)[M x K] . op(B)[K x N] (+ bias[N]),  row-major, optionally strided-batched.
  *   opA == 0: A stored M x K with row stride lda;  opA == 1: A stored K x M (row stride lda), used transposed.
  *   opB == 0: B stored K x N with row stride ldb;  opB == 1: B stored N x K (row stride ldb), used transposed.
- * in_dtype in {F32, BF16}; out_dtype == in_dtype or F32; bias (may be NULL) has dtype bias_dtype (F32 or out_dtype).
+ * in_dtype in {F32, BF16, F16 (since 0.5.0)}; out_dtype == in_dtype or F32; bias (may be NULL) has dtype bias_dtype (F32 or
+ * out_dtype).
  * autotune > 1: on the first call of a problem, time the library's top `autotune` (<= 64) heuristic candidates on the
  * given operands (the product is recomputed, beta == 0) and keep the fastest; a problem listed in an imported tuning
  * table starts with the recorded choice instead.  Returns BB_EUNSUPPORTED (-3) when the
@@ -821,7 +832,8 @@ int bevbert_val_auc(const int64_t* sorted_keys, int64_t n, int64_t* out, void* s
 
 /* ---- CLIP vision transformer (csrc/vit.hip, clip_vit.py): forward-only row kernels ------------------------------------
  * Rows are (rows, H) row-major, H in {256, 512, 768, 1024}; the residual stream z32 is fp32 whatever `dtype` (the
- * compute dtype of the GEMM operands: BB_F32 or BB_BF16). */
+ * compute dtype of the GEMM operands: BB_F32 or BB_BF16; since 0.5.0 also BB_F16 for the four bevbert_vit_* entries, whose
+ * fp16 results are the fp32 value rounded to nearest even, overflow to inf). */
 
 /* ConvertImageDtype + Normalize + conv1's im2col: images (n_src, R, R, 3) u8 -> out (N * g * g, 3 * P * P) dtype with
  * g = R / P, P in {16, 32}, column order (c, ky, kx); output image i reads input image view_map[i] (NULL: i; an index

@@ -1,10 +1,12 @@
 """ms per panorama batch (12 * batch images) of the device-side CLIP ViT-B/16 encoder (vln_bevbert_amd.clip_vit), eager and
-replayed from one hipGraph, with fp32 and with bf16 operands, next to a plain-torch fp16 restatement of the same network
+replayed from one hipGraph, with fp32, bf16 and fp16 operands, next to a plain-torch fp16 restatement of the same network
 (F.scaled_dot_product_attention, fp16 stream, fp32 LayerNorm statistics: the arithmetic of the reference's GPU path) on the
 same GPU in the same process, the variants taking turns.  Device events, after warm-up, at least a second of device work per
-variant.  Also the algorithmic FLOP, the resulting TF/s, and bytes / time / TB/s of the row kernels at the batch's rows.
+variant.  Also the algorithmic FLOP, the resulting TF/s, bytes / time / TB/s of the row kernels at the batch's rows, and the
+attention call alone at the step's shape (batch * 12 images, 12 heads, 197 tokens): the fp16 kernel (csrc/attn_f16.hip) against
+the kernel the dispatch plan gives bf16, in turns.
 
-    python scripts/bench_clip_vit.py [--batch 16] [--seconds 1.0] [--out profiles/clip_vit_bench.txt]
+    python scripts/bench_clip_vit.py [--batch 16] [--seconds 1.0] [--out profiles/clip_vit_bench.txt [--append]]
 """
 import argparse
 import os
@@ -15,9 +17,10 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from vln_bevbert_amd import clip_vit as V  # noqa: E402
-from vln_bevbert_amd import weights  # noqa: E402
+from vln_bevbert_amd import lib, ops, weights  # noqa: E402
 
 CFG = (224, 16, 768, 12, 12, 512)
+MODES = (("fp32", torch.float32), ("bf16", torch.bfloat16), ("fp16", torch.float16))
 
 
 def algorithmic_flop(cfg, n):
@@ -94,6 +97,7 @@ def main():
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--seconds", type=float, default=1.0)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--append", action="store_true", help="add to --out instead of replacing it")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     n = a.batch * 12
@@ -104,7 +108,7 @@ def main():
     sd.update({k: 1 + 5 * v for k, v in sd.items() if "ln_" in k and k.endswith(".weight")})     # gains around 1
     u8 = torch.randint(0, 256, (n, R, R, 3), generator=g, dtype=torch.uint8).to(dev)
     variants, graphs = {}, []
-    for tag, dt in (("fp32", torch.float32), ("bf16", torch.bfloat16)):
+    for tag, dt in MODES:
         m = V.ClipVisionTransformer(*CFG)
         m.load_state_dict(sd, strict=True)
         m.finalize(dev, dt, n)
@@ -126,15 +130,35 @@ def main():
     for k, v in ms.items():
         lines.append(f"  {k:28s} {v:9.3f} ms / batch   {flop / v / 1e9:7.1f} TF/s   ({calls[k]} calls timed)")
     base = ms["torch fp16 restatement"]
-    for k in ("hip bf16 hipGraph replay", "hip fp32 hipGraph replay"):
+    for k in ("hip bf16 hipGraph replay", "hip fp16 hipGraph replay", "hip fp32 hipGraph replay"):
         lines.append(f"  torch fp16 restatement / {k}: {base / ms[k]:.2f}")
+    lines.append(f"  hip fp16 hipGraph replay / hip bf16 hipGraph replay: "
+                 f"{ms['hip fp16 hipGraph replay'] / ms['hip bf16 hipGraph replay']:.3f}")
+
+    # the attention call alone at the step's shape, the two 16-bit kernels in turns
+    L = (R // P) ** 2 + 1
+    qkv = torch.randn(n, L, 3 * W, generator=g).to(dev)
+    attn, paths = {}, {}
+    with torch.no_grad():
+        for tag, dt in MODES[1:]:
+            t = qkv.to(dt)
+            ops.attention_self(t, None, None, heads)
+            paths[tag] = lib.load().bevbert_attn_last_path(0).decode() if dt == torch.bfloat16 else "attn_f16_fwd"
+            attn[f"attention {tag} ({paths[tag]})"] = (lambda t=t: ops.attention_self(t, None, None, heads))
+        ams, acalls = take_turns(attn, a.seconds / 4)
+    aflop = 2 * 2 * n * heads * L * L * 64
+    lines.append(f"  attention alone, {n} images x {heads} heads x {L} tokens (packed qkv, event-timed, in turns):")
+    for k, v in ams.items():
+        lines.append(f"    {k:34s} {v * 1e3:8.1f} us / call   {aflop / v / 1e9:7.1f} TF/s   ({acalls[k]} calls timed)")
+    fp16_name, bf16_name = [k for k in ams if " fp16 " in k][0], [k for k in ams if " bf16 " in k][0]
+    lines.append(f"    fp16 kernel / bf16 kernel: {ams[fp16_name] / ams[bf16_name]:.3f}; {layers} calls per batch")
 
     # the row kernels on their own, at the batch's rows
     rows, prow, C4 = n * ((R // P) ** 2 + 1), n * (R // P) ** 2, 4 * W
     lines.append(f"  row kernels at {rows} token rows ({prow} patch rows), bytes moved / time / rate:")
     gen = torch.Generator().manual_seed(1)
     vec = lambda k: torch.randn(k, generator=gen).to(dev)      # noqa: E731
-    for tag, dt in (("fp32", torch.float32), ("bf16", torch.bfloat16)):
+    for tag, dt in MODES:
         e = 4 if dt == torch.float32 else 2
         patches = torch.empty(prow, 3 * P * P, dtype=dt, device=dev)
         conv = torch.randn(prow, W, device=dev).to(dt)
@@ -159,8 +183,8 @@ def main():
     print(text)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+        with open(a.out, "a" if a.append else "w") as f:
+            f.write(("\n" if a.append else "") + text + "\n")
 
 
 if __name__ == "__main__":

@@ -12,10 +12,12 @@ in a hipGraph in front of waypoint_step / CEGraphMap:
     depth_grid_pool         AdaptiveAvgPool2d((14, 14)) of the depth images
     encode_panorama         both, with the reference's clockwise re-ordering of the views folded into the first kernels
 
-Arithmetic: the residual stream is fp32 (csrc/vit.hip), the GEMM and attention operands are in the compute dtype (fp32 or
-bf16); GEMMs go through ops.linear (hipBLASLt, cached plans), attention through ops.attention_self with batch = images.
+Arithmetic: the residual stream is fp32 (csrc/vit.hip), the GEMM and attention operands are in the compute dtype (fp32,
+bf16 or fp16); GEMMs go through ops.linear (hipBLASLt, cached plans), attention through ops.attention_self with batch =
+images.  float16 is the operand precision the reference itself runs (convert_weights): its attention is the forward-only
+kernel of csrc/attn_f16.hip, and since the predictor takes fp32 / bf16 only, encode_panorama widens the fp16 class vectors.
 The depth ResNet encoder is depth_resnet.py (encode_observations there runs both on one view map).
-Not built: CLIP's text tower, fp16 operands, any backward.
+Not built: CLIP's text tower, an fp16 depth encoder or predictor, any backward.
 """
 import ctypes
 
@@ -32,6 +34,8 @@ CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
 CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
 _MEAN_STD = (ctypes.c_float * 6)(*CLIP_MEAN, *CLIP_STD)
 LN_EPS = 1e-5
+# operand dtypes of the GEMMs and the attention; float16 is what the reference runs (clip/model.py convert_weights)
+COMPUTE_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
 
 
 class _Holder(nn.Module):
@@ -94,8 +98,8 @@ def _want(fn, name, t, dtype, shape):
 
 
 def _want_compute(fn, name, t):
-    if not torch.is_tensor(t) or t.dtype not in (torch.float32, torch.bfloat16) or t.dim() != 2:
-        raise ValueError(f"{fn}: {name} must be a float32 or bfloat16 (rows, width) tensor")
+    if not torch.is_tensor(t) or t.dtype not in COMPUTE_DTYPES or t.dim() != 2:
+        raise ValueError(f"{fn}: {name} must be a float32, bfloat16 or float16 (rows, width) tensor")
 
 
 def embed_prenorm(conv_out, class_embedding, pos, ln_pre, ln_1, L, z32=None, y=None, eps=LN_EPS):
@@ -242,8 +246,8 @@ class ClipVisionTransformer(nn.Module):
         ops.attention_self own them), and so do the two results, which belong to the caller: after the first call nothing
         is taken from the device and nothing synchronises.  Loading other weights retires what finalize built: call it
         again."""
-        if compute_dtype not in (torch.float32, torch.bfloat16):
-            raise ValueError("compute dtype must be float32 or bfloat16")
+        if compute_dtype not in COMPUTE_DTYPES:
+            raise ValueError("compute dtype must be float32, bfloat16 or float16")
         self.to(device)
         for p in self.parameters():
             p.requires_grad_(False)
@@ -371,12 +375,14 @@ def clockwise_view_map(B, device):
     return t
 
 
-def encode_panorama(encoder, rgb_u8, depth):
+def encode_panorama(encoder, rgb_u8, depth, embeds_dtype=None):
     """Mode 'waypoint' in front of the predictor: rgb_u8 (B, 12, R, R, 3) uint8 and depth (B, 12, Hd, Wd, 1) fp32 in the
-    simulator's counter-clockwise view order -> (rgb_embeds (B * 12, output_dim) in the compute dtype, rgb_grid
-    (B, 12, g * g, width) fp32, depth_grid (B, 12, 14, 14) fp32) in the reference's clockwise order: what waypoint_step
-    and CEGraphMap.remember_pano take as they are.  ``encoder``: a finalized ClipRGBEncoder or ClipVisionTransformer with
-    max_images >= B * 12.  The re-ordering is an index map read by the patch and pooling kernels, not a copy."""
+    simulator's counter-clockwise view order -> (rgb_embeds (B * 12, output_dim), rgb_grid (B, 12, g * g, width) fp32,
+    depth_grid (B, 12, 14, 14) fp32) in the reference's clockwise order: what waypoint_step and CEGraphMap.remember_pano
+    take as they are.  ``encoder``: a finalized ClipRGBEncoder or ClipVisionTransformer with max_images >= B * 12.  The
+    re-ordering is an index map read by the patch and pooling kernels, not a copy.  ``embeds_dtype``: the dtype of
+    rgb_embeds; None = the compute dtype of an fp32 / bf16 encoder, and fp32 for an fp16 encoder (the predictor takes fp32
+    and bf16 only; fp16 -> fp32 is exact, one elementwise launch over B * 12 x output_dim values, no synchronisation)."""
     vit = encoder.model.visual if isinstance(encoder, ClipRGBEncoder) else encoder
     if rgb_u8.dim() != 5 or rgb_u8.shape[1] != NUM_VIEWS or depth.dim() != 5 or tuple(depth.shape[:2]) != tuple(rgb_u8.shape[:2]):
         raise ValueError("encode_panorama: rgb (B, 12, R, R, 3) uint8 and depth (B, 12, Hd, Wd, 1) float32 expected")
@@ -384,4 +390,8 @@ def encode_panorama(encoder, rgb_u8, depth):
     vmap = clockwise_view_map(B, rgb_u8.device)
     x, x_patch = vit.encode_u8(rgb_u8.reshape((B * NUM_VIEWS,) + tuple(rgb_u8.shape[2:])), vmap)
     dgrid = depth_grid_pool(depth.reshape((B * NUM_VIEWS,) + tuple(depth.shape[2:])), vmap)
-    return x, x_patch.view(B, NUM_VIEWS, x_patch.shape[1], x_patch.shape[2]), dgrid.view(B, NUM_VIEWS, GRID, GRID)
+    if embeds_dtype is None and x.dtype == torch.float16:
+        embeds_dtype = torch.float32
+    if embeds_dtype is not None and x.dtype != embeds_dtype:
+        x = x.to(embeds_dtype)
+    return x,x_patch.view(B, NUM_VIEWS, x_patch.shape[1], x_patch.shape[2]), dgrid.view(B, NUM_VIEWS, GRID, GRID)

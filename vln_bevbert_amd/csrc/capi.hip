@@ -37,7 +37,7 @@ BEVBERT_API int bevbert_zero(void* p, int64_t bytes, hipStream_t stream) {
   return BB_OK;
 }
 
-BEVBERT_API int bevbert_version(void) { return 400; }  // 0.4.0: object grounding of the fine-tune rollout (csrc/nav_obj.hip)
+BEVBERT_API int bevbert_version(void) { return 500; }  // 0.5.0: float16 attention forward (csrc/attn_f16.hip), fp16 ViT row kernels and GEMMs
 
 static const uint32_t* g_step_salt = nullptr;
 const uint32_t* bb_step_salt() { return g_step_salt; }

@@ -402,7 +402,7 @@ int run_plan(Plan& p, const void* A, const void* B, void* C, const void* bias, f
 
 int check_problem(const Problem& q) {
   BB_REQUIRE(q.M > 0 && q.N > 0 && q.K > 0 && q.batch >= 1, "gemm: empty problem M=%d N=%d K=%d batch=%d", q.M, q.N, q.K, q.batch);
-  BB_REQUIRE(q.in_dtype == BB_F32 || q.in_dtype == BB_BF16, "gemm: input dtype %d unsupported", q.in_dtype);
+  BB_REQUIRE(q.in_dtype == BB_F32 || q.in_dtype == BB_BF16 || q.in_dtype == BB_F16, "gemm: input dtype %d unsupported", q.in_dtype);
   BB_REQUIRE(q.out_dtype == BB_F32 || q.out_dtype == q.in_dtype, "gemm: output dtype %d unsupported", q.out_dtype);
   BB_REQUIRE(q.bias_dtype < 0 || q.bias_dtype == BB_F32 || q.bias_dtype == q.out_dtype, "gemm: bias dtype %d unsupported", q.bias_dtype);
   return BB_OK;

@@ -159,6 +159,12 @@ template <> __device__ __forceinline__ float quickgelu_of<float>(float t) { retu
 template <> __device__ __forceinline__ float quickgelu_of<bf16_raw>(float t) {
   return t * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(t * -2.45546696148071f));   // 1.702 * log2(e)
 }
+// fp16 results take the same form.  The two hardware functions are good to 1 ulp of fp32 each and the product adds one
+// rounding: a relative error of about 2^-22 wherever the sigmoid is not negligible, a thousand times below the 2^-12 (half
+// an ulp) of the fp16 rounding that follows; the rounded argument of the exponential moves the result by |1.702 t| 2^-24
+// relative to the exponential, which only counts where the quotient is already tiny (t < 0) or the exponential is (t > 0).
+// t + bias is formed in fp32, so a result beyond 65504 becomes inf in the store's conversion, as IEEE fp16 does.
+template <> __device__ __forceinline__ float quickgelu_of<_Float16>(float t) { return quickgelu_of<bf16_raw>(t); }
 template <typename T> __device__ __forceinline__ float4 quickgelu4_of(float4 a, float4 b) {
   return make_float4(quickgelu_of<T>(a.x + b.x), quickgelu_of<T>(a.y + b.y), quickgelu_of<T>(a.z + b.z),
                      quickgelu_of<T>(a.w + b.w));
@@ -226,7 +232,7 @@ BEVBERT_API int bevbert_vit_patchify(const uint8_t* images, const int* view_map,
   for (int c = 0; c < 3; ++c) { nm.mean[c] = mean_std[c]; nm.std[c] = mean_std[3 + c]; }
   const int64_t rows = (int64_t)N * (R / P) * (R / P);
   const dim3 grid((unsigned)((rows + 3) / 4));
-  const bool type_ok = bb_with_type(dtype, [&](auto t) {
+  const bool type_ok = bb_with_type_of<float, bf16_raw, _Float16>(dtype, [&](auto t) {
     using T = decltype(t);
     bb_with_int<16, 32>(P, [&](auto p) {
       hipLaunchKernelGGL((vit_patchify_kernel<T, decltype(p)::value>), grid, dim3(256), 0, stream, images, view_map, (T*)out, N,
@@ -247,7 +253,7 @@ BEVBERT_API int bevbert_vit_embed_prenorm(const void* conv_out, const float* cla
   const int rows = N * L;
   const dim3 grid((rows + 3) / 4);
   bool width_ok = false;
-  const bool type_ok = bb_with_type(dtype, [&](auto t) {
+  const bool type_ok = bb_with_type_of<float, bf16_raw, _Float16>(dtype, [&](auto t) {
     using T = decltype(t);
     width_ok = bb_with_width<1, 2, 3, 4>(H, [&](auto nv) {
       hipLaunchKernelGGL((vit_embed_prenorm_kernel<T, decltype(nv)::value>), grid, dim3(256), 0, stream, (const T*)conv_out,
@@ -269,7 +275,7 @@ BEVBERT_API int bevbert_vit_bias_residual_prenorm(float* z32, const void* x, con
   if (rows == 0) return BB_OK;
   const dim3 grid((rows + 3) / 4);
   bool width_ok = false;
-  const bool type_ok = bb_with_type(dtype, [&](auto t) {
+  const bool type_ok = bb_with_type_of<float, bf16_raw, _Float16>(dtype, [&](auto t) {
     using T = decltype(t);
     width_ok = bb_with_width<1, 2, 3, 4>(H, [&](auto nv) {
       bb_with_bool(final_form != 0, [&](auto fin) {
@@ -289,7 +295,7 @@ BEVBERT_API int bevbert_vit_bias_quickgelu(const void* x, const float* bias, voi
   BB_REQUIRE(rows >= 0 && C > 0 && C % 4 == 0, "vit_bias_quickgelu: rows=%d C=%d (C must be a multiple of 4)", rows, C);
   if (rows == 0) return BB_OK;
   const dim3 grid(elementwise_row_groups(rows), (C + 1023) / 1024);
-  const bool type_ok = bb_with_type(dtype, [&](auto t) {
+  const bool type_ok = bb_with_type_of<float, bf16_raw, _Float16>(dtype, [&](auto t) {
     using T = decltype(t);
     hipLaunchKernelGGL(vit_bias_quickgelu_kernel<T>, grid, dim3(256), 0, stream, (const T*)x, bias, (T*)y, rows, C);
   });

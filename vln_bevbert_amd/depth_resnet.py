@@ -373,13 +373,14 @@ class DepthResNetEncoder(nn.Module):
         return self.encode(observations["depth"].contiguous())
 
 
-def encode_observations(rgb_encoder, depth_encoder, rgb_u8, depth):
+def encode_observations(rgb_encoder, depth_encoder, rgb_u8, depth, embeds_dtype=None):
     """Mode 'waypoint' in front of the predictor, both backbones: rgb_u8 (B, 12, R, R, 3) uint8 and depth (B, 12, H, W, 1)
     fp32 in the simulator's counter-clockwise view order -> {"rgb_embeds" (B * 12, 512), "rgb_grid" (B, 12, 196, 768) fp32,
     "depth_grid" (B, 12, 14, 14) fp32, "depth_embeds" (B * 12, 128, 4, 4)} in the reference's clockwise order; the embeddings
     are in the encoders' compute dtype and are what waypoint_step takes as they are.  One clockwise_view_map serves every
-    stage.  Both encoders are finalized with max_images >= B * 12."""
-    rgb_embeds, rgb_grid, depth_grid = encode_panorama(rgb_encoder, rgb_u8, depth)
+    stage.  Both encoders are finalized with max_images >= B * 12.  ``embeds_dtype`` is encode_panorama's: the dtype of
+    "rgb_embeds" (None: the RGB encoder's compute dtype, fp32 for a float16 encoder)."""
+    rgb_embeds, rgb_grid, depth_grid = encode_panorama(rgb_encoder, rgb_u8, depth, embeds_dtype)
     B = rgb_u8.shape[0]
     depth_embeds = depth_encoder.encode(depth.reshape((B * NUM_VIEWS,) + tuple(depth.shape[2:])),
                                         clockwise_view_map(B, depth.device))

@@ -200,15 +200,60 @@ def graph_bias(dists, weight, bias, layers, nh):
     return outs
 
 
+def _is_f16(*ts):
+    return any(t is not None and t.dtype == torch.float16 for t in ts)
+
+
+def _attention_f16(mode, a, b_, c_, key_mask, bias, nh, drop_p):
+    """float16 operands: the forward-only kernel of csrc/attn_f16.hip (bevbert_attn_f16_fwd) -- softmax(q k^T / 8) v with fp32
+    scores and accumulation, nothing else.  What that kernel does not do is refused here, before any launch: a key mask, a
+    bias, dropout, gradients, mixed dtypes.  (bevbert_attn_fwd / _bwd reject float16.)"""
+    ts = [t for t in (a, b_, c_) if t is not None]
+    if any(t.dtype != torch.float16 for t in ts):
+        raise ValueError(f"float16 attention: every operand must be float16, got {[t.dtype for t in ts]}")
+    if key_mask is not None or bias is not None:
+        raise ValueError("float16 attention is the inference kernel of the CLIP image encoder: it takes no key mask and no bias")
+    if drop_p > 0:
+        raise ValueError("float16 attention has no dropout (forward-only inference kernel)")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in ts):
+        raise ValueError("float16 attention has no backward: detach the operands or run under torch.no_grad()")
+    if any(t.dim() != 3 or t.stride(2) != 1 for t in ts):
+        raise ValueError("float16 attention: operands are (B, L, width) with unit inner stride")
+    if mode == "self":
+        H = a.shape[-1] // 3
+        q, k, v = a[..., :H], a[..., H:2 * H], a[..., 2 * H:]
+    elif mode == "cross":
+        H = a.shape[-1]
+        q, k, v = a, b_[..., :H], b_[..., H:]
+    else:
+        H = a.shape[-1]
+        q, k, v = a, b_, c_
+    if H != nh * HEAD_DIM or k.shape[-1] != H or v.shape[-1] != H:
+        raise ValueError(f"float16 attention: width {H} is not nh * {HEAD_DIM} = {nh * HEAD_DIM} for q, k and v alike")
+    if k.shape[0] != q.shape[0] or v.shape[0] != q.shape[0] or v.shape[1] != k.shape[1] or q.shape[1] < 1 or k.shape[1] < 1:
+        raise ValueError(f"float16 attention: shapes q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)}")
+    B, Lq, Lk = q.shape[0], q.shape[1], k.shape[1]
+    o = torch.empty(B, Lq, H, dtype=torch.float16, device=q.device)
+    call("bevbert_attn_f16_fwd", ptr(q), ptr(k), ptr(v), ptr(o), _strides(q, k, v, o), B, nh, Lq, Lk, HEAD_DIM,
+         1.0 / math.sqrt(HEAD_DIM), stream())
+    return o
+
+
 def attention_self(qkv, key_mask, bias, nh, drop_p=0.0, training=False):
+    if _is_f16(qkv):
+        return _attention_f16("self", qkv, None, None, key_mask, bias, nh, drop_p if training else 0.0)
     return _Attention.apply("self", qkv, None, None, key_mask, bias, nh, drop_p if training else 0.0, RT.attn_impl)
 
 
 def attention_cross(q, kv, key_mask, nh, drop_p=0.0, training=False):
+    if _is_f16(q, kv):
+        return _attention_f16("cross", q, kv, None, key_mask, None, nh, drop_p if training else 0.0)
     return _Attention.apply("cross", q, kv, None, key_mask, None, nh, drop_p if training else 0.0, RT.attn_impl)
 
 
 def attention(q, k, v, key_mask=None, bias=None, nh=12, drop_p=0.0, training=False, impl=None):
+    if _is_f16(q, k, v):
+        return _attention_f16("sep", q, k, v, key_mask, bias, nh, drop_p if training else 0.0)
     return _Attention.apply("sep", q, k, v, key_mask, bias, nh, drop_p if training else 0.0,
                             RT.attn_impl if impl is None else impl)
 

@@ -129,7 +129,7 @@ def _rows(t):
 
 
 def _lt_ok(*ts):
-    return _LT_ENABLED and all(t.is_cuda and t.dtype in (torch.float32, torch.bfloat16) for t in ts)
+    return _LT_ENABLED and all(t.is_cuda and t.dtype in (torch.float32, torch.bfloat16, torch.float16) for t in ts)
 
 
 def _linear_fwd(x, w_c, b_c):
