@@ -120,7 +120,7 @@ int bevbert_attn_drop_bits(uint64_t* drop_bits, int B, int nh, int Lq, int Lk, f
  * bits_ready = 0 -- the forward hashes inline and leaves the bits behind for the backward (small score matrices). */
 int bevbert_attn_bits_ahead(int Lq, int Lk, int has_bias);
 
-/* Float16 attention forward (since 0.5.0; entry point added, ABI otherwise unchanged; csrc/attn_f16.hip): the attention of
+/* Float16 attention forward (since 0.5.0; entry point added, ABI otherwise unchanged; csrc/attn_fwd2.hip): the attention of
  * the CLIP image encoder's float16 mode, inference only.  o = softmax(q k^T * scale) v with fp16 q / k / v / o (B, L, nh*64)
  * and the stride block of bevbert_attn_fwd; no key mask, no bias, no dropout, no lse.  Any Lq, Lk >= 1, head_dim 64.
  * Scores, maximum and row sum are fp32; P is rounded to fp16 (nearest even) for the P V product, which accumulates in

@@ -3,7 +3,7 @@ replayed from one hipGraph, with fp32, bf16 and fp16 operands, next to a plain-t
 (F.scaled_dot_product_attention, fp16 stream, fp32 LayerNorm statistics: the arithmetic of the reference's GPU path) on the
 same GPU in the same process, the variants taking turns.  Device events, after warm-up, at least a second of device work per
 variant.  Also the algorithmic FLOP, the resulting TF/s, bytes / time / TB/s of the row kernels at the batch's rows, and the
-attention call alone at the step's shape (batch * 12 images, 12 heads, 197 tokens): the fp16 kernel (csrc/attn_f16.hip) against
+attention call alone at the step's shape (batch * 12 images, 12 heads, 197 tokens): the fp16 kernel (csrc/attn_fwd2.hip) against
 the kernel the dispatch plan gives bf16, in turns.
 
     python scripts/bench_clip_vit.py [--batch 16] [--seconds 1.0] [--out profiles/clip_vit_bench.txt [--append]]
@@ -143,7 +143,7 @@ def main():
         for tag, dt in MODES[1:]:
             t = qkv.to(dt)
             ops.attention_self(t, None, None, heads)
-            paths[tag] = lib.load().bevbert_attn_last_path(0).decode() if dt == torch.bfloat16 else "attn_f16_fwd"
+            paths[tag] = lib.load().bevbert_attn_last_path(0).decode() if dt == torch.bfloat16 else "attn_fwd2_f16"
             attn[f"attention {tag} ({paths[tag]})"] = (lambda t=t: ops.attention_self(t, None, None, heads))
         ams, acalls = take_turns(attn, a.seconds / 4)
     aflop = 2 * 2 * n * heads * L * L * 64

@@ -1,4 +1,4 @@
-"""Inputs, bound, cases and a CPU emulation for the float16 attention forward (csrc/attn_f16.hip, bevbert_attn_f16_fwd), shared
+"""Inputs, bound, cases and a CPU emulation for the float16 attention forward (csrc/attn_fwd2.hip, bevbert_attn_f16_fwd), shared
 by tests/test_gpu_attn_f16.py (the kernel) and tests/test_clip_vit_f16_host.py (the emulation, on the same tensors).  Nothing
 here touches the library.
 

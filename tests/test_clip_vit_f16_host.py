@@ -1,5 +1,5 @@
 """CPU: what the float16 operand mode of the CLIP image encoder (clip_vit.py finalize(compute_dtype=torch.float16),
-csrc/attn_f16.hip) has to achieve, from an emulation of exactly its arithmetic, and the conditions the GPU tests lean on.
+csrc/attn_fwd2.hip) has to achieve, from an emulation of exactly its arithmetic, and the conditions the GPU tests lean on.
 
 The emulation is tests/clip_ref.py's forward with the data flow of clip_vit._encode_patches: GEMM and attention operands and
 every stored activation rounded to the compute dtype, products summed in fp32, the residual stream, the LayerNorms, QuickGELU

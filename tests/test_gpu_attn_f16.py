@@ -1,4 +1,4 @@
-"""csrc/attn_f16.hip on the GPU: bevbert_attn_f16_fwd (through ops.attention_self / attention_cross / attention and
+"""csrc/attn_fwd2.hip with fp16 operands on the GPU: bevbert_attn_f16_fwd (through ops.attention_self / attention_cross / attention and
 directly) per element against the fp64 softmax-attention of its fp16-rounded inputs, at every length where the kernel's tiling
 turns over (tests/attn_f16_cases.py: inputs, bound and case list; tests/test_clip_vit_f16_host.py holds the bound against a
 CPU emulation of the kernel's arithmetic and against one wrong key at a tile edge).

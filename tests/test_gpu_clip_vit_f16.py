@@ -1,5 +1,5 @@
 """The float16 operand mode of the CLIP image encoder on the GPU (csrc/vit.hip instantiated for _Float16, fp16 library GEMMs,
-csrc/attn_f16.hip; clip_vit.py finalize(compute_dtype=torch.float16)): the row kernels against torch / fp64 math, the model
+csrc/attn_fwd2.hip; clip_vit.py finalize(compute_dtype=torch.float16)): the row kernels against torch / fp64 math, the model
 against the reference's recorded outputs within the project's factor of the reference's OWN fp16 error
 (tests/golden/clip_vit.npz; tests/test_clip_vit_f16_host.py derives what to expect), capture, and the hand-over of an fp16
 encoder's outputs to the fp32 / bf16 predictor.  Every figure is printed before it is asserted.

@@ -15,7 +15,7 @@ in a hipGraph in front of waypoint_step / CEGraphMap:
 Arithmetic: the residual stream is fp32 (csrc/vit.hip), the GEMM and attention operands are in the compute dtype (fp32,
 bf16 or fp16); GEMMs go through ops.linear (hipBLASLt, cached plans), attention through ops.attention_self with batch =
 images.  float16 is the operand precision the reference itself runs (convert_weights): its attention is the forward-only
-kernel of csrc/attn_f16.hip, and since the predictor takes fp32 / bf16 only, encode_panorama widens the fp16 class vectors.
+instance of csrc/attn_fwd2.hip, and since the predictor takes fp32 / bf16 only, encode_panorama widens the fp16 class vectors.
 The depth ResNet encoder is depth_resnet.py (encode_observations there runs both on one view map).
 Not built: CLIP's text tower, an fp16 depth encoder or predictor, any backward.
 """

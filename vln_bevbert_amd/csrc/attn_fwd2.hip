@@ -1,4 +1,4 @@
-// K2 forward, second generation (bf16 in / fp32 accumulate): the same transposed MFMA formulation as attn_mfma.hip
+// K2 forward, second generation (bf16 or fp16 in / fp32 accumulate): the same transposed MFMA formulation as attn_mfma.hip
 //   S^T = K Q^T  (lane q = l & 15 holds S[q][key = 16 t + 4 g + r]),   O^T = V^T P^T  (P goes D -> B operand in place)
 // on a VALU diet.  The round-2 kernel issued 23 VALU instructions per matrix instruction with dropout (13 without):
 // it was bound by the vector pipe, not by MFMA, LDS or HBM (profiles/r02f_pmc_attn_sq_counters.txt).  Here:
@@ -16,11 +16,25 @@
 //     CU (16 waves).  Workgroups of 7 waves (two cover the 441 BEV cells with 1.6 % padding) were slower: DESIGN.md.
 // Per score element: max3 (1/2), fma, exp2, add, cndmask (dropout only), cvt_pk (1/2)  =  4 - 5 vector instructions per
 // matrix instruction.
+//
+// The kernel is one template over the operand type (OperandBf16 / OperandF16, attn_mfma_common.h).  Its float16 instance
+// (fp16 q, k, v, o; v_mfma_f32_16x16x32_f16) is the attention of the CLIP image encoder's float16 mode (clip_vit.py), where
+// the reference runs the converted fp16 network.  Inference only: no key mask, no bias, no dropout, no log-sum-exp; an
+// entry of its own (bevbert_attn_f16_fwd, capi.hip), outside the dispatch plan of bevbert_attn_fwd.  Any Lq, Lk >= 1, as
+// for bf16: keys past Lk enter as -inf through the C operand of the first Q K^T instruction of their tile, query rows
+// past Lq are computed on a clamped row and not stored.  Rounding of the float16 instance:
+//   * scores, the running maximum and the row sum are fp32; the row sum adds the UNROUNDED probabilities;
+//   * P = exp2(s * scale * log2e - m) is rounded to fp16 to nearest even (v_cvt_pk_f16_f32) for the P V product.  m lags the
+//     true maximum by at most FWD2_THR, so P <= 2^FWD2_THR = 32, far from fp16's 65504; and a lagging m only makes P LARGER
+//     than exp(s - max), so a probability that is a normal fp16 number relative to its row maximum (>= 2^-14) stays one;
+//   * O = (sum_j P_j V_j) * (1 / l): the reciprocal is an IEEE fp32 division, the product one fp32 multiply (2 ulp of fp32
+//     together, 2^-12 of an fp16 ulp), then ONE rounding to fp16 -- overflow gives inf as IEEE fp16 does, nothing saturates.
 #include "attn_mfma_common.h"
 
 #define FWD2_THR 5.0f
 
-// K / V tiles of this kernel: [64 rows][64 bf16] at a row stride of 72 elements (144 B).  Measured on the MI355X at
+// K / V tiles of this kernel: [64 rows][64 16-bit words] at a row stride of 72 elements (144 B), moved as raw words (the
+// staging and the transposing read never interpret them).  Measured with bf16 on the MI355X at
 // B = 64, 441 x 441 (gpurun_out r03d / r03k / r03l): 144-byte rows with four 4-wave workgroups per CU 87.7 / 76.4 us
 // (dropout 0.1 / none); 160-byte rows (conflict-free in scripts/lds_bank_sim.py, but 41.5 KB per workgroup -> three per
 // CU) 116 / 100 us; 128-byte rows with an XOR swizzle of the 16-byte chunks (conflict-free, 33 KB, but the per-lane
@@ -30,28 +44,35 @@
 #define F2_TILE (TK * F2_LD)
 #define F2_NW 4       // waves per workgroup, 32 queries each
 __device__ __forceinline__ int f2_off(int row, int chunk) { return row * F2_LD + (chunk << 3); }
-__device__ __forceinline__ bf16x8 f2_frag_rows(const bf16_raw* tile, int t, int ks, int lane) {
-  return as_bf16x8(*reinterpret_cast<const uint4*>(tile + f2_off(t * 16 + (lane & 15), ks * 4 + (lane >> 4))));
+template <typename Op>
+__device__ __forceinline__ typename Op::frag f2_frag_rows(const bf16_raw* tile, int t, int ks, int lane) {
+  return Op::as_frag(*reinterpret_cast<const uint4*>(tile + f2_off(t * 16 + (lane & 15), ks * 4 + (lane >> 4))));
 }
 // fragment whose eight k-slots of lane group g are image rows row_lo + (0..3) and row_hi + (0..3), at columns col0 .. +15
-__device__ __forceinline__ bf16x8 f2_frag_tr(const bf16_raw* img, int row_lo, int row_hi, int col0, int lane) {
+template <typename Op>
+__device__ __forceinline__ typename Op::frag f2_frag_tr(const bf16_raw* img, int row_lo, int row_hi, int col0, int lane) {
   const int i = lane & 15, col = col0 + 4 * (i & 3);
   const int rl = row_lo + (i >> 2), rh = row_hi + (i >> 2);
   const uint2 lo = lds_tr16(img + f2_off(rl, col >> 3) + (col & 7));
   const uint2 hi = lds_tr16(img + f2_off(rh, col >> 3) + (col & 7));
-  return as_bf16x8(make_uint4(lo.x, lo.y, hi.x, hi.y));
+  return Op::as_frag(make_uint4(lo.x, lo.y, hi.x, hi.y));
 }
 
 // (Named fwd3: the round-3 kernel of this file on a further diet -- fused multiply-add before the maximum, select before
 // the packed conversion, keep-bit words of a whole tile requested in front of the tile barrier; see the comments inside.)
-template <bool DROP>
+// Op::MASK_LSE false (float16, DROP false only): the instance reads no key mask and stores no log-sum-exp.
+template <typename Op, bool DROP>
 __global__ __launch_bounds__(64 * F2_NW, 4) void attn_fwd3_kernel(AttnArgs a) {
+  typedef typename Op::frag frag;
   constexpr int NW = F2_NW;
   constexpr int QT = 2;                      // 16-query tiles per wave
   constexpr int NT = 64 * NW;
-  constexpr int CPT = (512 + NT - 1) / NT;   // 16-byte chunks of a [64][64] bf16 tile per thread.  NT = 256 divides 512, so
-  // the ``ch < 512`` tests below never fail; the compiler cannot see that and the kernel's code changes without them
-  // (1 208 instead of 1 313 instructions with dropout), so they stay until a change that measures the difference
+  constexpr int CPT = (512 + NT - 1) / NT;   // 16-byte chunks of a [64][64] tile per thread.  NT = 256 divides 512, so
+  // the ``ch < 512`` tests below never fail; the compiler cannot see that and the bf16 kernels' code changes without them
+  // (1 208 instead of 1 313 instructions with dropout), so they stay there until a change that measures the difference.
+  // The float16 instance was written and measured without them
+  constexpr bool CH_GUARD = Op::MASK_LSE;
+  static_assert(CPT * NT == 512, "the staging loops cover a tile exactly");
   __shared__ __attribute__((aligned(16))) bf16_raw s_k[2][F2_TILE];
   __shared__ __attribute__((aligned(16))) bf16_raw s_v[2][F2_TILE];
   __shared__ __attribute__((aligned(16))) float s_mask[2][TK];
@@ -66,14 +87,14 @@ __global__ __launch_bounds__(64 * F2_NW, 4) void attn_fwd3_kernel(AttnArgs a) {
   const float sc2 = a.scale * LOG2E;
   const float inv_scale = 1.0f / a.scale;
 
-  bf16x8 qf[QT][2];
+  frag qf[QT][2];
   int qrow[QT];
 #pragma unroll
   for (int qt = 0; qt < QT; ++qt) {
     qrow[qt] = qbase + qt * 16 + c;
     const int r = qrow[qt] < a.Lq ? qrow[qt] : a.Lq - 1;
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) qf[qt][ks] = as_bf16x8(ld_frag_global(qp, a.ldq, r, ks * 32 + g * 8));
+    for (int ks = 0; ks < 2; ++ks) qf[qt][ks] = Op::as_frag(ld_frag_global(qp, a.ldq, r, ks * 32 + g * 8));
   }
   // keep-bit words of this wave's query tiles: 16 words (t, r) per (query tile, 64-key tile), 64-key tiles contiguous
   bb_cu64p wq[QT];
@@ -100,7 +121,7 @@ __global__ __launch_bounds__(64 * F2_NW, 4) void attn_fwd3_kernel(AttnArgs a) {
   auto mask_of = [&](int kv0) -> float {
     const int key = kv0 + tid;
     if (tid >= TK || key >= a.Lk) return -INFINITY;
-    return a.key_mask ? a.key_mask[(size_t)b * a.Lk + key] * inv_scale : 0.f;
+    return Op::MASK_LSE && a.key_mask ? a.key_mask[(size_t)b * a.Lk + key] * inv_scale : 0.f;
   };
   uint4 kreg[CPT], vreg[CPT];
   float mreg;
@@ -109,7 +130,7 @@ __global__ __launch_bounds__(64 * F2_NW, 4) void attn_fwd3_kernel(AttnArgs a) {
     for (int i = 0; i < CPT; ++i) {
       const int ch = tid + i * NT, row = ch >> 3, d0 = (ch & 7) * 8;
       kreg[i] = vreg[i] = make_uint4(0, 0, 0, 0);                  // rows past the end are zero filled
-      if (ch < 512 && kv0 + row < a.Lk) {
+      if ((!CH_GUARD || ch < 512) && kv0 + row < a.Lk) {
         kreg[i] = ld_frag_global(kp, a.ldk, kv0 + row, d0);
         vreg[i] = ld_frag_global(vp, a.ldv, kv0 + row, d0);
       }
@@ -120,7 +141,7 @@ __global__ __launch_bounds__(64 * F2_NW, 4) void attn_fwd3_kernel(AttnArgs a) {
 #pragma unroll
     for (int i = 0; i < CPT; ++i) {
       const int ch = tid + i * NT, row = ch >> 3, d0 = (ch & 7) * 8;
-      if (ch < 512) {
+      if (!CH_GUARD || ch < 512) {
         *reinterpret_cast<uint4*>(s_k[buf] + f2_off(row, ch & 7)) = kreg[i];
         *reinterpret_cast<uint4*>(s_v[buf] + f2_off(row, ch & 7)) = vreg[i];
       }
@@ -156,9 +177,9 @@ __global__ __launch_bounds__(64 * F2_NW, 4) void attn_fwd3_kernel(AttnArgs a) {
         for (int qt = 0; qt < QT; ++qt) sacc[qt][tt] = (f32x4){mk.x, mk.y, mk.z, mk.w};
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-          const bf16x8 kf = f2_frag_rows(ck, t, ks, lane);
+          const frag kf = f2_frag_rows<Op>(ck, t, ks, lane);
 #pragma unroll
-          for (int qt = 0; qt < QT; ++qt) sacc[qt][tt] = mfma16(kf, qf[qt][ks], sacc[qt][tt]);
+          for (int qt = 0; qt < QT; ++qt) sacc[qt][tt] = Op::mfma(kf, qf[qt][ks], sacc[qt][tt]);
         }
       }
       // ---- first half: stage tile j+1 into the other buffer (its last readers passed the barrier that closed
@@ -203,9 +224,9 @@ __global__ __launch_bounds__(64 * F2_NW, 4) void attn_fwd3_kernel(AttnArgs a) {
         }
       }
       // ---- P = exp2(t); row sums before dropout; keep bits straight from scalar registers; the empty asm pins the
-      //      select in front of the bf16 conversion (the compiler otherwise converts each element alone, selects on the
+      //      select in front of the 16-bit conversion (the compiler otherwise converts each element alone, selects on the
       //      16-bit halves and merges them with v_perm: 2.5 instead of 1.5 vector instructions per element)
-      bf16x8 pb[QT];
+      frag pb[QT];
 #pragma unroll
       for (int qt = 0; qt < QT; ++qt) {
         float psum = 0.f;
@@ -222,14 +243,14 @@ __global__ __launch_bounds__(64 * F2_NW, 4) void attn_fwd3_kernel(AttnArgs a) {
             sacc[qt][tt][r] = p;
           }
         l_run[qt] += psum;
-        pb[qt] = pack_pair(sacc[qt][0], sacc[qt][1]);
+        pb[qt] = Op::pack(sacc[qt][0], sacc[qt][1]);
       }
       // ---- O^T += V^T P^T over this half's 32 keys: k-slot (g, j) <-> key 32 hh + 16 (j >> 2) + 4 g + (j & 3)
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
-        const bf16x8 vf = f2_frag_tr(cv, 32 * hh + 4 * g, 32 * hh + 16 + 4 * g, dt * 16, lane);
+        const frag vf = f2_frag_tr<Op>(cv, 32 * hh + 4 * g, 32 * hh + 16 + 4 * g, dt * 16, lane);
 #pragma unroll
-        for (int qt = 0; qt < QT; ++qt) oacc[qt][dt] = mfma16(vf, pb[qt], oacc[qt][dt]);
+        for (int qt = 0; qt < QT; ++qt) oacc[qt][dt] = Op::mfma(vf, pb[qt], oacc[qt][dt]);
       }
 
     }
@@ -257,12 +278,12 @@ __global__ __launch_bounds__(64 * F2_NW, 4) void attn_fwd3_kernel(AttnArgs a) {
     const float l = quad_sum(l_run[qt]);
     const float inv = ks / l;
     if (qrow[qt] < a.Lq) {
-      bf16_raw* op = (bf16_raw*)a.o + (size_t)b * a.bso + (size_t)qrow[qt] * a.ldo + h * ATTN_D;
+      typename Op::store_t* op = (typename Op::store_t*)a.o + (size_t)b * a.bso + (size_t)qrow[qt] * a.ldo + h * ATTN_D;
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt)
-        st4<bf16_raw>(op + dt * 16 + g * 4, make_float4(oacc[qt][dt][0] * inv, oacc[qt][dt][1] * inv,
-                                                         oacc[qt][dt][2] * inv, oacc[qt][dt][3] * inv));
-      if (a.lse && g == 0) a.lse[((size_t)b * a.nh + h) * a.Lq + qrow[qt]] = (log2f(l) - nm[qt]) * LN2;
+        st4<typename Op::store_t>(op + dt * 16 + g * 4, make_float4(oacc[qt][dt][0] * inv, oacc[qt][dt][1] * inv,
+                                                                    oacc[qt][dt][2] * inv, oacc[qt][dt][3] * inv));
+      if (Op::MASK_LSE && a.lse && g == 0) a.lse[((size_t)b * a.nh + h) * a.Lq + qrow[qt]] = (log2f(l) - nm[qt]) * LN2;
     }
   }
 }
@@ -393,8 +414,19 @@ int attn_fwd2(const AttnArgs& a_in, hipStream_t st) {
   AttnArgs a = a_in;
   a.nblk = (a.Lq + 32 * F2_NW - 1) / (32 * F2_NW);
   const dim3 grid((unsigned)a.nblk * a.nh * a.B);
-  if (a.drop_p > 0.f) hipLaunchKernelGGL((attn_fwd3_kernel<true>), grid, dim3(64 * F2_NW), 0, st, a);
-  else hipLaunchKernelGGL((attn_fwd3_kernel<false>), grid, dim3(64 * F2_NW), 0, st, a);
+  if (a.drop_p > 0.f) hipLaunchKernelGGL((attn_fwd3_kernel<OperandBf16, true>), grid, dim3(64 * F2_NW), 0, st, a);
+  else hipLaunchKernelGGL((attn_fwd3_kernel<OperandBf16, false>), grid, dim3(64 * F2_NW), 0, st, a);
   BB_CHECK_LAUNCH("attn_fwd(mfma, gen 2)");
+  return BB_OK;
+}
+
+// float16 operands (bevbert_attn_f16_fwd): the caller passes no key mask, no bias, no dropout and no lse
+int attn_fwd2_f16(const AttnArgs& a_in, hipStream_t st) {
+  BB_REQUIRE(attn_mfma_operands_aligned(a_in, false), "attn_f16_fwd: " ATTN_MFMA_ALIGN_MSG);
+  AttnArgs a = a_in;
+  a.nblk = (a.Lq + 32 * F2_NW - 1) / (32 * F2_NW);
+  BB_REQUIRE((int64_t)a.nblk * a.nh * a.B < (int64_t)1 << 31, "attn_f16_fwd: too many workgroups");
+  hipLaunchKernelGGL((attn_fwd3_kernel<OperandF16, false>), dim3((unsigned)(a.nblk * a.nh * a.B)), dim3(64 * F2_NW), 0, st, a);
+  BB_CHECK_LAUNCH("attn_f16_fwd");
   return BB_OK;
 }

@@ -139,22 +139,38 @@ __device__ __forceinline__ bf16x8 lds_frag_tr(const bf16_raw* img, int stride, i
   return as_bf16x8(make_uint4(lo.x, lo.y, hi.x, hi.y));
 }
 
-// ---- float16 operands (attn_f16.hip) ------------------------------------------------------------------------------------
+// ---- operand traits: what interprets the 16-bit words -------------------------------------------------------------------
 // v_mfma_f32_16x16x32_f16 has the operand layout and the rate of the bf16 instruction, and every helper above that only
-// moves 16-bit words (ld_frag_global, lds_tr16, the tile staging) serves both: an fp16 kernel passes its tiles as the raw
-// 16-bit storage type.  Only what interprets the bits gets a twin here.
+// moves 16-bit words (ld_frag_global, lds_tr16, the tile staging) serves both: a kernel written over one of these traits
+// passes its tiles as the raw 16-bit storage type and goes through the trait for the fragment type, the matrix
+// instruction, the packed conversion of P and the type its output is stored as (st4<store_t>).
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 bb_f16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x4 mfma16h(f16x8 a, f16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f16x8 as_f16x8(uint4 u) { return __builtin_bit_cast(f16x8, u); }
 // one v_cvt_pk_f16_f32 per pair: round to nearest even, overflow to inf (IEEE; the pkrtz form truncates)
 __device__ __forceinline__ uint32_t pack_f16x2(float lo, float hi) {
   const bb_f32x2_t v = {lo, hi};
   return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bb_f16x2));
 }
-__device__ __forceinline__ f16x8 pack_pair_f16(const f32x4& a, const f32x4& b) {
-  return as_f16x8(make_uint4(pack_f16x2(a[0], a[1]), pack_f16x2(a[2], a[3]), pack_f16x2(b[0], b[1]),
-                             pack_f16x2(b[2], b[3])));
-}
+struct OperandBf16 {
+  typedef bf16x8 frag;
+  typedef bf16_raw store_t;
+  // kernels over these operands take the additive key mask and write the log-sum-exp (training and inference)
+  static constexpr bool MASK_LSE = true;
+  static __device__ __forceinline__ frag as_frag(uint4 u) { return as_bf16x8(u); }
+  static __device__ __forceinline__ f32x4 mfma(frag a, frag b, f32x4 c) { return mfma16(a, b, c); }
+  static __device__ __forceinline__ frag pack(const f32x4& a, const f32x4& b) { return pack_pair(a, b); }
+};
+struct OperandF16 {
+  typedef f16x8 frag;
+  typedef _Float16 store_t;
+  // float16 is the forward-only inference mode of the CLIP image encoder: no key mask, no log-sum-exp
+  static constexpr bool MASK_LSE = false;
+  static __device__ __forceinline__ frag as_frag(uint4 u) { return __builtin_bit_cast(f16x8, u); }
+  static __device__ __forceinline__ f32x4 mfma(frag a, frag b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+  }
+  static __device__ __forceinline__ frag pack(const f32x4& a, const f32x4& b) {
+    return as_frag(make_uint4(pack_f16x2(a[0], a[1]), pack_f16x2(a[2], a[3]), pack_f16x2(b[0], b[1]),
+                              pack_f16x2(b[2], b[3])));
+  }
+};

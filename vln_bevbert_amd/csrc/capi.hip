@@ -37,7 +37,7 @@ BEVBERT_API int bevbert_zero(void* p, int64_t bytes, hipStream_t stream) {
   return BB_OK;
 }
 
-BEVBERT_API int bevbert_version(void) { return 500; }  // 0.5.0: float16 attention forward (csrc/attn_f16.hip), fp16 ViT row kernels and GEMMs
+BEVBERT_API int bevbert_version(void) { return 500; }  // 0.5.0: float16 attention forward (csrc/attn_fwd2.hip), fp16 ViT row kernels and GEMMs
 
 static const uint32_t* g_step_salt = nullptr;
 const uint32_t* bb_step_salt() { return g_step_salt; }
@@ -69,6 +69,7 @@ int attn_mfma_bwd(const AttnArgs& a, hipStream_t st);
 int attn_mfma_bwd1(const AttnArgs& a, hipStream_t st);
 bool attn_mfma_bwd1_supported(const AttnArgs& a);
 int attn_fwd2(const AttnArgs& a, hipStream_t st);
+int attn_fwd2_f16(const AttnArgs& a, hipStream_t st);
 bool attn_fwd2_supported(const AttnArgs& a);
 int attn_drop_bits(const AttnArgs& a, uint64_t* bits_f, uint64_t* bits_b, uint32_t* bits_l, hipStream_t st);
 int attn_fwd4(const AttnArgs& a, const uint32_t* bits_l, hipStream_t st);
@@ -316,6 +317,22 @@ BEVBERT_API int bevbert_attn_bwd(const void* q, const void* k, const void* v, co
     case AK_attn_f32_bwd: return attn_f32_bwd(a, stream);
     default: return attn_simple_bwd(a, dtype, stream);
   }
+}
+
+// float16 operands: the forward-only instance of attn_fwd2.hip, outside the dispatch plan (no mask, bias, dropout or lse)
+BEVBERT_API int bevbert_attn_f16_fwd(const void* q, const void* k, const void* v, void* o, const int64_t* strides, int B,
+                                     int nh, int Lq, int Lk, int head_dim, float scale, hipStream_t stream) {
+  BB_REQUIRE(q != nullptr && k != nullptr && v != nullptr && o != nullptr && strides != nullptr,
+             "attn_f16_fwd: q, k, v, o and strides must not be NULL");
+  AttnArgs a;
+  int rc = fill_common(a, q, k, v, nullptr, nullptr, strides, B, nh, Lq, Lk, head_dim, scale, 0.f, 0, 0);
+  if (rc != BB_OK) return rc;
+  a.o = o;
+  const int64_t width = (int64_t)nh * ATTN_D;
+  BB_REQUIRE(a.ldq >= width && a.ldk >= width && a.ldv >= width && a.ldo >= width,
+             "attn_f16_fwd: row strides below nh * 64 = %ld", (long)width);
+  BB_REQUIRE(a.bsq >= 0 && a.bsk >= 0 && a.bsv >= 0 && a.bso >= 0, "attn_f16_fwd: negative batch stride");
+  return attn_fwd2_f16(a, stream);
 }
 
 // An argument block with the shape and the presence flags of a call and operands that pass every alignment check

@@ -37,6 +37,18 @@ def _bits_ahead(Lq, Lk, has_bias):
     return load().bevbert_attn_bits_ahead(Lq, Lk, int(has_bias))
 
 
+def _split_qkv(mode, a, b_, c_):
+    """(H, q, k, v) of an attention call.  mode 'self': qkv packed (B,L,3H);  'cross': q (B,Lq,H) + kv packed (B,Lk,2H);
+    'sep': q, k, v.  The slices are views of the packed operands."""
+    if mode == "self":
+        H = a.shape[-1] // 3
+        return H, a[..., :H], a[..., H:2 * H], a[..., 2 * H:]
+    H = a.shape[-1]
+    if mode == "cross":
+        return H, a, b_[..., :H], b_[..., H:]
+    return H, a, b_, c_
+
+
 class _Attention(torch.autograd.Function):
     """mode 'self': qkv packed (B,L,3H);  mode 'cross': q (B,Lq,H) + kv packed (B,Lk,2H);  mode 'sep': q,k,v."""
 
@@ -44,15 +56,7 @@ class _Attention(torch.autograd.Function):
     def forward(ctx, mode, a, b_, c_, key_mask, bias, nh, drop_p, impl):
         # (an operand expanded over the batch shares its rows: the kernels would write every batch's gradient to one place)
         a, b_, c_ = (t.contiguous() if t is not None and _expanded(t) else t for t in (a, b_, c_))
-        if mode == "self":
-            H = a.shape[-1] // 3
-            q, k, v = a[..., :H], a[..., H:2 * H], a[..., 2 * H:]
-        elif mode == "cross":
-            H = a.shape[-1]
-            q, k, v = a, b_[..., :H], b_[..., H:]
-        else:
-            H = a.shape[-1]
-            q, k, v = a, b_, c_
+        H, q, k, v = _split_qkv(mode, a, b_, c_)
         assert H == nh * HEAD_DIM
         B, Lq, Lk = q.shape[0], q.shape[1], k.shape[1]
         o = torch.empty(B, Lq, H, dtype=q.dtype, device=q.device)
@@ -93,15 +97,12 @@ class _Attention(torch.autograd.Function):
         a, b_, c_, key_mask, bias, o, lse, bits = ctx.saved_tensors
         mode, nh, drop_p, seed, off, impl, scale = ctx.cfg
         do = do.contiguous()
+        H, q, k, v = _split_qkv(mode, a, b_, c_)
         if mode == "self":
-            H = a.shape[-1] // 3
-            q, k, v = a[..., :H], a[..., H:2 * H], a[..., 2 * H:]
             da = _grad_like(a)
             dq, dk, dv = da[..., :H], da[..., H:2 * H], da[..., 2 * H:]
             grads = (da, None, None)
         elif mode == "cross":
-            H = a.shape[-1]
-            q, k, v = a, b_[..., :H], b_[..., H:]
             dq = _grad_like(a)
             # K/V projected for all layers of an encoder at once (hoisted_kv): the gradient goes straight into this
             # layer's column slice of the shared (B, Lk, layers * 2H) buffer, which feeds ONE input-gradient GEMM
@@ -110,7 +111,6 @@ class _Attention(torch.autograd.Function):
             dk, dv = dkv[..., :H], dkv[..., H:]
             grads = (dq, dkv, None)
         else:
-            q, k, v = a, b_, c_
             dq, dk, dv = _grad_like(a), _grad_like(b_), _grad_like(c_)
             grads = (dq, dk, dv)
         B, Lq, Lk = q.shape[0], q.shape[1], k.shape[1]
@@ -205,7 +205,7 @@ def _is_f16(*ts):
 
 
 def _attention_f16(mode, a, b_, c_, key_mask, bias, nh, drop_p):
-    """float16 operands: the forward-only kernel of csrc/attn_f16.hip (bevbert_attn_f16_fwd) -- softmax(q k^T / 8) v with fp32
+    """float16 operands: the forward-only instance of csrc/attn_fwd2.hip (bevbert_attn_f16_fwd) -- softmax(q k^T / 8) v with fp32
     scores and accumulation, nothing else.  What that kernel does not do is refused here, before any launch: a key mask, a
     bias, dropout, gradients, mixed dtypes.  (bevbert_attn_fwd / _bwd reject float16.)"""
     ts = [t for t in (a, b_, c_) if t is not None]
@@ -219,15 +219,7 @@ def _attention_f16(mode, a, b_, c_, key_mask, bias, nh, drop_p):
         raise ValueError("float16 attention has no backward: detach the operands or run under torch.no_grad()")
     if any(t.dim() != 3 or t.stride(2) != 1 for t in ts):
         raise ValueError("float16 attention: operands are (B, L, width) with unit inner stride")
-    if mode == "self":
-        H = a.shape[-1] // 3
-        q, k, v = a[..., :H], a[..., H:2 * H], a[..., 2 * H:]
-    elif mode == "cross":
-        H = a.shape[-1]
-        q, k, v = a, b_[..., :H], b_[..., H:]
-    else:
-        H = a.shape[-1]
-        q, k, v = a, b_, c_
+    H, q, k, v = _split_qkv(mode, a, b_, c_)
     if H != nh * HEAD_DIM or k.shape[-1] != H or v.shape[-1] != H:
         raise ValueError(f"float16 attention: width {H} is not nh * {HEAD_DIM} = {nh * HEAD_DIM} for q, k and v alike")
     if k.shape[0] != q.shape[0] or v.shape[0] != q.shape[0] or v.shape[1] != k.shape[1] or q.shape[1] < 1 or k.shape[1] < 1:
