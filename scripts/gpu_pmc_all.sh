@@ -93,7 +93,7 @@ for m, r in sorted(recs.items()):
 for k, v in out.items():
     if k.startswith("attention:attn_fwd4"):
         bench_keys["bevbert_attn_fwd[Lq=441,Lk=441]"] = v["traffic_bytes"]
-    if k.startswith("attention:attn_bwd3"):
+    if k.startswith("attention:attn_bwd7p1_kernel<3"):
         bench_keys["bevbert_attn_bwd[Lq=441,Lk=441]"] = v["traffic_bytes"]
     if k.startswith("attention:attn_drop_bits"):
         bench_keys["bevbert_attn_drop_bits[Lq=441,Lk=441]"] = v["traffic_bytes"]

@@ -85,7 +85,7 @@ print(f"PyTorch eager kernels in the step: {sum(c for _, c, _ in tk) / K:.1f} la
 for n, c, t in sorted(tk, key=lambda x: -x[2]):
     print(f"  {c / K:6.1f} calls/step {t / 1e3 / c:8.2f} us avg {t / 1e6 / K:7.3f} ms/step  {n[:150]}")
 
-# The hand-written kernels per PROBLEM: one kernel symbol serves several shapes of a step (attn_bwd2_kernel: the 441 x 441
+# The hand-written kernels per PROBLEM: one kernel symbol serves several shapes of a step (attn_bwd7p1_kernel: the 441 x 441
 # BEV self-attention and the 80 x 441 text <- BEV cross-attention share a symbol AND a launch grid).  The kernel trace
 # carries no kernel arguments, so launches are keyed by (symbol, grid) and then split into duration clusters (sorted
 # durations, a new cluster wherever the next one is more than 1.35 x the previous): each line is one problem size, its

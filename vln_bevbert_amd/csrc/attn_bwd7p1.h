@@ -1,5 +1,5 @@
-// Shared by the two generations of the 7 + 1-wave single-pass backward (attn_bwd2.hip: round 3, attn_bwd3.hip: round 5):
-// LDS map, the packed bf16 dot product.
+// The 7 + 1-wave single-pass backward (attn_bwd7p1.hip, generations 2 and 3 of one kernel body): LDS map, the packed bf16
+// dot product.  No code that ends up in the kernel besides dot2_bf16: the shared parts of the body are lambdas inside it.
 #pragma once
 #include "attn_mfma_common.h"
 

@@ -390,7 +390,7 @@ __global__ __launch_bounds__(256) void attn_drop_bits_kernel(AttnArgs a, uint64_
 }
 
 int attn_drop_bits(const AttnArgs& a, uint64_t* bits_f, uint64_t* bits_b, uint32_t* bits_l, hipStream_t st) {
-  // the backward layout is only read by the 7+1-wave backward (attn_bwd3.hip: 256 < Lk <= 448, no bias), the per-lane
+  // the backward layout is only read by the 7+1-wave backward (attn_bwd7p1.hip: 256 < Lk <= 448, no bias), the per-lane
   // layout by the one-workgroup-per-head forward (attn_fwd4.hip, same key range): both are written for that key range
   const bool with_b = bits_b != nullptr && bits_l != nullptr && a.bias == nullptr && a.Lk > 256 && a.Lk <= 448;
   const int total = a.B * a.nh * (with_b ? a.nq16 / 4 : a.nq16) * a.nk64;

@@ -205,7 +205,7 @@ static AttnKernel attn_plan_bwd(const AttnArgs& a, int dtype, int impl, const At
     // one pass over the scores when all keys of a (batch, head) fit one workgroup (attn_bwd1.hip); BEVBERT_ATTN_BWD=split
     // forces the two-kernel path (A/B measurements), and so does impl 3
     if (kn.bwd_split || im == 3) return AK_attn_mfma_bwd;
-    // BEVBERT_ATTN_BWD=1: the round-2 single-pass kernel where the 7+1-wave kernel (attn_bwd2.hip) would run
+    // BEVBERT_ATTN_BWD=1: the round-2 single-pass kernel where the 7+1-wave kernel (attn_bwd7p1.hip) would run
     if (!kn.bwd_gen1) {
       // round 6: query and key sequences up to 96 without a graph bias (80 x 80 text, 36 x 36 panoramas, 17 x 80 / 80 x 17
       // map <-> text): attn_short.hip
@@ -216,7 +216,7 @@ static AttnKernel attn_plan_bwd(const AttnArgs& a, int dtype, int impl, const At
       // BEVBERT_ATTN_SMALL=1: the one-wave backward for short key sequences and any query count (BEV <- text, 441 x 80)
       if (kn.small && attn_small_bwd_supported(a)) return AK_attn_small_bwd;
       // BEV self-attention and text -> BEV (256 < Lk <= 448, no bias): the 7+1-wave kernel.  BEVBERT_ATTN_BWD3=0: its
-      // round-3 loop (attn_bwd2.hip) where the round-5 one (attn_bwd3.hip) would run -- A/B measurements and the on-GPU
+      // round-3 loop (attn_bwd7p1.hip, GEN 2) where the round-5 one (GEN 3) would run -- A/B measurements and the on-GPU
       // cross-check
       if (kn.bwd3 && attn_bwd3_supported(a)) return AK_attn_bwd3;
       if (attn_bwd2_supported(a)) return AK_attn_bwd2;
