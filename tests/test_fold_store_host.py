@@ -229,10 +229,9 @@ def test_an_arena_whose_trainer_exchanges_gradients_never_stores(model_arena, ca
     assert [c[0] for c in calls] == ["bevbert_grad_norm_clip", "bevbert_adamw_step"]
 
 
-def test_the_trainer_allows_store_mode_only_alone_on_a_gpu_without_early_flush():
-    assert fold_store_allowed("cuda", False, False, env={})
-    assert not fold_store_allowed("cuda", True, False, env={})          # gradients change after the fold (all-reduce)
-    assert not fold_store_allowed("cuda", False, True, env={})          # two folds per step
-    assert not fold_store_allowed("cpu", False, False, env={})
-    assert not fold_store_allowed("cuda", False, False, env={"BEVBERT_FOLD_STORE": "0"})
-    assert fold_store_allowed("cuda", False, False, env={"BEVBERT_FOLD_STORE": "1"})
+def test_the_trainer_allows_store_mode_only_alone_on_a_gpu():
+    assert fold_store_allowed("cuda", False, env={})
+    assert not fold_store_allowed("cuda", True, env={})          # gradients change after the fold (all-reduce)
+    assert not fold_store_allowed("cpu", False, env={})
+    assert not fold_store_allowed("cuda", False, env={"BEVBERT_FOLD_STORE": "0"})
+    assert fold_store_allowed("cuda", False, env={"BEVBERT_FOLD_STORE": "1"})

@@ -154,6 +154,47 @@ def test_attention_sources_read_only_the_listed_switches():
         assert any(f"`{name}`" in line for line in table), f"README.md's environment table has no row for {name}"
 
 
+# Every environment variable the rest of the package reads.  A new entry needs a README row, and -- if it selects a code
+# path -- a test, script or benchmark line that runs the path behind it; one that selects a path nothing runs goes, with
+# its path.
+PACKAGE_KNOBS = (
+    # select a code path: a test, a script or bench.py sets it, or reaches the attribute / function that reads it
+    # (BEVBERT_LT_GEMM=0 forces the fallback that problems without a plan take anyway: ops.GEMM_FALLBACKS)
+    "BEVBERT_GRAPHS", "BEVBERT_OVERLAP_ZERO", "BEVBERT_GRAD_EXCHANGE", "BEVBERT_FOLD_STORE", "BEVBERT_RES32_Y32",
+    "BEVBERT_NAV_TEXT_CACHE", "BEVBERT_WGRAD_STREAM", "BEVBERT_WGRAD_STREAMS", "BEVBERT_DEFER_FINALIZE", "BEVBERT_LT_GEMM",
+    "BEVBERT_GEMM_TUNING",
+    # guards against machine behaviour (hwqueues.py, the collective's queue)
+    "BEVBERT_COPY_STREAM_PROBE", "BEVBERT_STEER_POOL", "BEVBERT_COLLECTIVE_QUEUE_CHECK",
+    # sizes, counts and locations: no second code path
+    "BEVBERT_WGRAD_BATCH", "BEVBERT_SCRATCH_MB", "BEVBERT_SCRATCH_MAX_MB", "BEVBERT_SCRATCH_INITIAL_MB", "BEVBERT_SPLITK_MAX",
+    "BEVBERT_LT_AUTOTUNE", "BEVBERT_LT_PLAN_BUDGET", "BEVBERT_LT_WS_MB", "BEVBERT_LT_EXHAUSTIVE", "BEVBERT_GEMM_DETERMINISTIC",
+    "BEVBERT_GEMM_TABLE", "BEVBERT_TXT_PAD", "BEVBERT_PANO_PAD", "BEVBERT_VIEW_PAD", "BEVBERT_OBJ_PAD",
+    "BEVBERT_REDUCE_TEXT_LAYERS", "BEVBERT_LIBHDF5")
+
+
+def test_package_sources_read_only_the_listed_switches():
+    """What ATTN_KNOBS is to the attention sources, PACKAGE_KNOBS is to everything else: the quoted BEVBERT_* names in the
+    package's Python modules and in the HIP sources the attention test does not cover are exactly that tuple, and README.md's
+    environment table has a row for each.  A switch added without both, or left behind by a retired path, fails here."""
+    pkg = os.path.dirname(lib.__file__)
+    csrc = os.path.join(pkg, "csrc")
+    paths = [os.path.join(pkg, f) for f in sorted(os.listdir(pkg)) if f.endswith(".py")]
+    paths += [os.path.join(csrc, f) for f in sorted(os.listdir(csrc))
+              if f.endswith((".hip", ".h")) and not re.fullmatch(r"attn_\w+\.(hip|h)|capi\.hip", f)]
+    assert len(paths) >= 50, paths
+    found = {}
+    for path in paths:
+        with open(path) as f:
+            for name in re.findall(r'"(BEVBERT_[A-Z0-9_]+)"', f.read()):
+                found.setdefault(name, os.path.basename(path))
+    assert len(set(PACKAGE_KNOBS)) == len(PACKAGE_KNOBS) and not set(PACKAGE_KNOBS) & set(ATTN_KNOBS)
+    assert set(found) == set(PACKAGE_KNOBS), sorted((n, found.get(n)) for n in set(found) ^ set(PACKAGE_KNOBS))
+    with open(os.path.join(os.path.dirname(pkg), "README.md")) as f:
+        table = [line for line in f if line.lstrip().startswith("|")]
+    for name in PACKAGE_KNOBS:
+        assert any(f"`{name}`" in line for line in table), f"README.md's environment table has no row for {name}"
+
+
 def attn_plan(l, row, ncu, monkeypatch):
     """(forward, backward) kernel names bevbert_attn_plan gives a row of ATTN_PLAN_ROWS under the row's knobs."""
     B, Lq, Lk, dtype, impl, bias, p, bits, env = row[:9]

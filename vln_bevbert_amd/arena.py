@@ -23,7 +23,6 @@ from .lib import ptr, stream
 from .ops_core import call          # the traced C-ABI call (bench.py's kernel-timing pass)
 
 CHUNK = 1024
-_ZERO_KERNEL = __import__("os").environ.get("BEVBERT_ZERO_KERNEL", "0") == "1"      # A/B: fill kernel instead of a memset command
 NO_DECAY = ("bias", "LayerNorm.bias", "LayerNorm.weight")   # optim/misc.py:14 (substring match)
 
 
@@ -372,10 +371,7 @@ class ParamArena:
                     self._zero_stream = side_stream(self.device)
                 self._zero_stream.wait_stream(torch.cuda.current_stream(self.device))
                 with torch.cuda.stream(self._zero_stream):
-                    if _ZERO_KERNEL:
-                        self.grads.zero_()
-                    else:
-                        call("bevbert_zero", ptr(self.grads), self.grads.numel() * 4, stream())
+                    call("bevbert_zero", ptr(self.grads), self.grads.numel() * 4, stream())
                 self._zero_pending = True
                 return
             call("bevbert_zero", ptr(self.grads), self.grads.numel() * 4, stream())

@@ -3,8 +3,7 @@
 #pragma once
 #include "common.h"
 
-// Defined once, in colwise.hip (they cache BEVBERT_COLWISE_MAX_BLOCKS / BEVBERT_ROWS_PER_BLOCK in function-local statics:
-// the LayerNorm backward and the column kernels must agree on the number of partial rows).
+// Defined once, in colwise.hip: the LayerNorm backward and the column kernels must agree on the number of partial rows.
 void launch_finalize(const float* partials, int nblocks, int nwhich, int C, float* o0, float* o1, float* o2,
                      int accumulate, hipStream_t stream);
 int colwise_max_blocks();

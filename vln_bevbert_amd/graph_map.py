@@ -16,7 +16,6 @@ Here:
   * Node embeddings live in ONE (B, cap, H) device tensor of running sums + a count tensor, updated functionally with
     two ``index_put`` per step (autograd flows through them across steps like it does through the reference's stored
     tensors) and read with one device gather.
-  * ``FloydGraph`` is the single-episode form of the same relaxation (kept for callers that want one graph).
   * Point clouds are never stored: a node remembers its row in the device-resident ``feature_store.GridFeatureStore``
     and its camera poses; ``bev_inputs`` returns, per sample, the store rows of the current viewpoint and its visited
     neighbours (``pc_order`` hops) in the order the reference concatenates them, the depths gathered from the store and
@@ -155,79 +154,6 @@ class Shipped:
             off, n, dt, shape, _ = self.meta[name]
             v = self._views[name] = self.buf[off:off + n].view(_torch_dtype(dt)).view(shape)
         return v
-
-
-class FloydGraph:
-    """graph_utils.py:44-94 on dense matrices.  Nodes are registered on their first edge (like the reference's
-    defaultdict keys) and keep their insertion order."""
-
-    def __init__(self, capacity=32):
-        self.index = {}
-        self.names = []
-        self._dis = np.full((capacity, capacity), float(_INF))
-        self._point = np.full((capacity, capacity), -1, dtype=np.int32)     # -1: direct edge ("" in the reference)
-        self._visited = set()
-
-    def _idx(self, x):
-        i = self.index.get(x)
-        if i is None:
-            i = self.index[x] = len(self.names)
-            self.names.append(x)
-            if i >= self._dis.shape[0]:
-                n = 2 * self._dis.shape[0]
-                dis = np.full((n, n), float(_INF))
-                pt = np.full((n, n), -1, dtype=np.int32)
-                dis[:i, :i], pt[:i, :i] = self._dis[:i, :i], self._point[:i, :i]
-                self._dis, self._point = dis, pt
-        return i
-
-    def __len__(self):
-        return len(self.names)
-
-    def distance(self, x, y):
-        if x == y:
-            return 0
-        i, j = self.index.get(x), self.index.get(y)
-        return float(_INF) if i is None or j is None else float(self._dis[i, j])
-
-    def add_edge(self, x, y, dis):
-        i, j = self._idx(x), self._idx(y)
-        if dis < self._dis[i, j]:
-            self._dis[i, j] = self._dis[j, i] = dis
-            self._point[i, j] = self._point[j, i] = -1
-
-    def update(self, k):
-        """Relax every pair through k (graph_utils.py:63-72).  Row / column k cannot change during the reference's
-        double loop (the diagonal stays 'infinite'), so one vectorised comparison is the same sequence of updates."""
-        kk = self._idx(k)
-        n = len(self.names)
-        d = self._dis[:n, :n]
-        via = d[:, kk][:, None] + d[kk, :][None, :]
-        better = via < d
-        np.fill_diagonal(better, False)
-        d[better] = via[better]
-        self._point[:n, :n][better] = kk
-        self._visited.add(k)
-
-    def visited(self, k):
-        return k in self._visited
-
-    def path(self, x, y):
-        if x == y:
-            return []
-        i, j = self.index[x], self.index[y]
-        k = self._point[i, j]
-        if k < 0:
-            return [y]
-        kn = self.names[k]
-        return self.path(x, kn) + self.path(kn, y)
-
-    def submatrix(self, names):
-        """Distances between the named nodes, (len, len) float64; 0 on the diagonal like ``distance``."""
-        idx = np.asarray([self.index[v] for v in names], dtype=np.int64)
-        m = self._dis[np.ix_(idx, idx)].copy()
-        np.fill_diagonal(m, 0.0)
-        return m
 
 
 class _EpisodeView:

@@ -27,8 +27,8 @@ from .ops_reduce import (  # noqa: F401
     defers_finalize)
 from .capture import join_captured_side_streams  # noqa: F401
 from .ops_gemm import (  # noqa: F401
-    GEMM_FALLBACKS, GEMM_TUNING_FILE, HOIST_KV, _HoistedKV, _KVGradHolder, _LT_AUTOTUNE, _LT_ENABLED, _LT_PLANS,
-    _LT_PLAN_BUDGET, _LT_RUN, _LT_UNSUPPORTED, _Linear, _LinearPacked, _PackedParam, _SPLITK_ENABLED, _SPLITK_MAX,
+    GEMM_FALLBACKS, GEMM_TUNING_FILE, _HoistedKV, _KVGradHolder, _LT_AUTOTUNE, _LT_ENABLED, _LT_PLANS,
+    _LT_PLAN_BUDGET, _LT_RUN, _LT_UNSUPPORTED, _Linear, _LinearPacked, _PackedParam, _SPLITK_MAX,
     _linear_dgrad, _linear_fwd, _linear_wgrad, _lt_gemm, _lt_ok, _param_grads, _rows, _split_k,
     _tuning_loaded, _warn_fallback, _wgrad_into, gemm_plan_count, hoisted_kv, linear, linear_packed, linear_packed_res,
     linear_res, load_gemm_tuning_table, save_gemm_tuning_table)

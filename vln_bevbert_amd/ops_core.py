@@ -112,11 +112,9 @@ class _AttnBitsPlanner:
     that belong to the plan -- the hashing (one 32-bit mix per element pair: ~80 us of pure VALU work per 441 x 441
     site at batch 64) then runs beside the library GEMMs of the text and panorama encoders instead of in front of
     every attention kernel, and each attention forward only waits for its site's event.  Works eagerly and inside a
-    captured step (the side stream is forked from and joined to the capturing stream).  BEVBERT_ATTN_BITS_AHEAD=0
-    turns it off (A/B measurements)."""
+    captured step (the side stream is forked from and joined to the capturing stream)."""
 
     def __init__(self):
-        self.enabled = _os.environ.get("BEVBERT_ATTN_BITS_AHEAD", "1") == "1"
         self.plans = {}          # key -> {"sites": [sig], "bufs": [tensor]}
         self.key = None
         self.seen = []
@@ -129,7 +127,7 @@ class _AttnBitsPlanner:
         if self.key is not None and self.seen and self.key not in self.plans:
             self.plans[self.key] = {"sites": list(self.seen), "bufs": [None] * len(self.seen)}
         self.key, self.seen, self.idx, self.ready = key, [], 0, None
-        if not self.enabled or key is None or not torch.cuda.is_available():
+        if key is None or not torch.cuda.is_available():
             return
         plan = self.plans.get(key)
         if plan is None:
@@ -188,10 +186,10 @@ class Branches:
     Autograd replays every backward op on the stream its forward ran on and inserts the cross-stream waits itself."""
 
     # Issued eagerly the extra fork / join events cost ~3 ms of host time per step at batch 64 and the step becomes
-    # host-bound (round 2, one call: 19.27 with vs 19.35 ms without), so the side stream is OFF for eager steps
-    # (BEVBERT_STREAMS=1 turns it on); CAPTURED steps turn it on themselves (train.PretrainTrainer.graph_branches),
-    # where the edges cost nothing on the host: 18.58 vs 19.32 ms/step.
-    enabled = _os.environ.get("BEVBERT_STREAMS", "0") == "1"
+    # host-bound (round 2, one call: 19.27 with vs 19.35 ms without), so the side stream is OFF for eager steps;
+    # CAPTURED steps turn it on themselves (train.PretrainTrainer._capture_stream_layout), where the edges cost nothing
+    # on the host: 18.58 vs 19.32 ms/step.
+    enabled = False
     _streams = {}
 
     def __init__(self, device):

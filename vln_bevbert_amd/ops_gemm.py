@@ -189,10 +189,7 @@ def _linear_wgrad(dy2, x2, S=1, scratch=False):
     return _on_launch_stream(lambda: dy2.t().mm(x2))
 
 
-_SPLITK_ENABLED = _os.environ.get("BEVBERT_SPLITK", "1") == "1"     # A/B knob
-
-
-_SPLITK_MAX = int(_os.environ.get("BEVBERT_SPLITK_MAX", "16"))
+_SPLITK_MAX = int(_os.environ.get("BEVBERT_SPLITK_MAX", "16"))      # most chunks; 1 = no split
 
 
 def _split_k(M, N, K):
@@ -201,8 +198,6 @@ def _split_k(M, N, K):
     The output is small (9..36 tiles of 256x256) and the reduction axis M is long (5 120 .. 28 224 tokens), so a plain
     GEMM leaves most of the 256 CUs idle (measured 140-250 TFLOP/s); a batched GEMM over S chunks of M fills them
     (600-880 TFLOP/s, scripts/bench_wgrad.py).  Aim at 144-256 workgroups, keep >= 640 tokens per chunk."""
-    if not _SPLITK_ENABLED:
-        return 1
     tiles = ((N + 255) // 256) * ((K + 255) // 256)
     s = 1
     while s * 2 <= min(_SPLITK_MAX, M // 640) and s * 2 * tiles <= 256 and M % (s * 2) == 0:
@@ -357,9 +352,6 @@ class _LinearPacked(torch.autograd.Function):
 
 def linear_packed(x, pw, pb):
     return _LinearPacked.apply(x, pw, pb)
-
-
-HOIST_KV = _os.environ.get("BEVBERT_HOIST_KV", "1") == "1"      # A/B knob
 
 
 class _KVGradHolder:

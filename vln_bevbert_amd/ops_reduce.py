@@ -28,10 +28,9 @@ class WgradStream:
     enabled = _os.environ.get("BEVBERT_WGRAD_STREAM", "1") == "1"
     BATCH = int(_os.environ.get("BEVBERT_WGRAD_BATCH", "6"))
     DEFER_FINALIZE = _os.environ.get("BEVBERT_DEFER_FINALIZE", "1") == "1"      # A/B knob for the split reductions
-    # own stream even next to ops.Branches (three streams).  Round 1 shared one side stream because three streams had
-    # stalled at batch 64: stream-K library GEMMs spinning on each other across streams (the
-    # package sets TENSILE_STREAMK_DATA_PARALLEL=1); three to four streams measure fastest
-    OWN_STREAM = _os.environ.get("BEVBERT_WGRAD_OWN_STREAM", "1") == "1"
+    # The stream is never the one of ops.Branches.  Round 1 shared one side stream because three streams had stalled at
+    # batch 64: stream-K library GEMMs spinning on each other across streams (the package sets
+    # TENSILE_STREAMK_DATA_PARALLEL=1); three to four streams measure fastest
     stream = None
     streams = []
     # BEVBERT_WGRAD_STREAMS=2: batches of deferred work alternate between two streams (independent weight-gradient GEMMs
@@ -73,9 +72,8 @@ class WgradStream:
         if not fns:
             return
         if cls.stream is None:
-            shared = Branches._streams.get(producer.device.index) if Branches.enabled and not cls.OWN_STREAM else None
             from .hwqueues import side_stream
-            cls.stream = shared if shared is not None else side_stream(producer.device)
+            cls.stream = side_stream(producer.device)
             Branches._streams["wgrad"] = cls.stream       # joined by ParamArena.sync / GradReducer like the branches
             cls._events = [torch.cuda.Event() for _ in range(64)]
             cls.streams = [cls.stream]

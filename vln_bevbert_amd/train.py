@@ -286,10 +286,10 @@ class GradReducer:
         self._done = []
 
 
-def fold_store_allowed(device_type, reducer_active, early_flush, env=None):
+def fold_store_allowed(device_type, reducer_active, env=None):
     """May the step's fold store and carry the clip norm (PretrainTrainer.__init__ explains the conditions)?"""
     env = os.environ if env is None else env
-    return env.get("BEVBERT_FOLD_STORE", "1") == "1" and device_type == "cuda" and not reducer_active and not early_flush
+    return env.get("BEVBERT_FOLD_STORE", "1") == "1" and device_type == "cuda" and not reducer_active
 
 
 class PretrainTrainer:
@@ -304,12 +304,6 @@ class PretrainTrainer:
         self.global_step = 0
         import os
         self.use_graphs = os.environ.get("BEVBERT_GRAPHS", "1") == "1" and arena.device.type == "cuda"
-        # captured steps fork the independent model branches (text || panorama encoder, global-map || BEV encoder) onto
-        # a third stream: in a graph the extra fork / join edges cost no host time (issued eagerly they cost ~3 ms of
-        # events per step and make the step host-bound), and the small text / map kernels overlap the 28 224-row ones.
-        # Measured in one call on one MI355X at batch 64: eager 18.83, graph with the weight-gradient stream only 19.32,
-        # + branch stream 18.58 ms/step.  BEVBERT_GRAPH_BRANCHES=0 turns it off.
-        self.graph_branches = os.environ.get("BEVBERT_GRAPH_BRANCHES", "1") == "1"
         # the gradient-arena fill runs on a side stream beside the forward pass (arena.zero_grad); BEVBERT_OVERLAP_ZERO=0: in line
         self.overlap_zero = os.environ.get("BEVBERT_OVERLAP_ZERO", "1") == "1" and arena.device.type == "cuda"
         self.graph_error = None            # set (and use_graphs cleared) if a capture ever fails
@@ -330,21 +324,15 @@ class PretrainTrainer:
             self.capture_ok = False      # a host-staged exchange (gloo on device tensors) is not stream work: eager steps
         if self.reducer.active:
             self.broadcast_state()             # replicas start from rank 0's weights, as under DistributedDataParallel
-        # Without collectives the same moment of backward -- d loss / d text-embeddings complete: every kernel of the two
-        # map encoders and the heads has been enqueued, 57 % of the parameter bytes -- is used to issue the batched
-        # reductions queued so far (split-K partial sums -> arena, LayerNorm / bias column sums): they then run on the
-        # weight-gradient stream beside the text encoder's backward instead of all at the END of backward, in front of
-        # clip + AdamW on the critical path (multi_accum alone is ~0.6 ms per step at batch 64).  MEASURED SLOWER (round 4,
-        # same box, two runs each: 18.40 vs 17.89 ms per step): the flush makes the weight-gradient streams join, which
-        # serialises work that otherwise overlaps the text encoder's backward.  Off unless BEVBERT_EARLY_FLUSH=1.
-        self.early_flush = os.environ.get("BEVBERT_EARLY_FLUSH", "0") == "1" and arena.device.type == "cuda"
-        if self.early_flush and not self.overlap:
-            model.bert.lang_encoder.register_forward_hook(self._hook_flush)
+        # The batched reductions queued during backward (split-K partial sums -> arena, LayerNorm / bias column sums) are
+        # issued once, at the END of backward: flushing them earlier, when backward reaches the text encoder, measured
+        # slower (18.40 vs 17.89 ms per step; the flush makes the weight-gradient streams join, which serialises work that
+        # otherwise overlaps the text encoder's backward).
         # Store-mode folds that carry the clip norm (ops.ReduceQueue, ParamArena.store_ok): this trainer zeroes the arena
         # before every backward pass, so the step's single fold may start from 0.f instead of reading the zeros back.  Not
-        # with a gradient exchange (the all-reduce changes the gradients after the fold: the norm must be taken afterwards)
-        # nor with the early flush (two folds per step).  BEVBERT_FOLD_STORE=0 turns it off (A/B).
-        arena.fold_store = fold_store_allowed(arena.device.type, self.reducer.active, self.early_flush)
+        # with a gradient exchange (the all-reduce changes the gradients after the fold: the norm must be taken afterwards).
+        # BEVBERT_FOLD_STORE=0 turns it off (A/B).
+        arena.fold_store = fold_store_allowed(arena.device.type, self.reducer.active)
         if self.overlap:
             self.install_map_layer_hooks()
             model.bert.lang_encoder.register_forward_hook(self._hook_text)
@@ -439,11 +427,6 @@ class PretrainTrainer:
             if torch.is_tensor(x) and x.requires_grad and torch.is_grad_enabled():
                 x.register_hook(lambda g: (self.reducer.launch_region(lo, hi), g)[1])
         return pre_hook
-
-    def _hook_flush(self, module, inputs, output):
-        if output.requires_grad and torch.is_grad_enabled():
-            output.register_hook(lambda g: (ops.WgradStream.flush_all(), g)[1])
-        return output
 
     def _hook_text(self, module, inputs, output):
         if output.requires_grad and torch.is_grad_enabled():
@@ -605,11 +588,15 @@ class PretrainTrainer:
 
     @contextlib.contextmanager
     def _capture_stream_layout(self):
-        """The stream layout of a captured step (``graph_branches``), for the capture and for the warm-up runs before it: the
-        order in which the deferred weight-gradient work is issued -- and with it the scratch addresses in the cached
-        reduction task tables -- depends on it."""
+        """The stream layout of a captured step, for the capture and for the warm-up runs before it: the order in which
+        the deferred weight-gradient work is issued -- and with it the scratch addresses in the cached reduction task
+        tables -- depends on it.  The independent model branches (text || panorama encoder, global-map || BEV encoder) fork
+        onto a third stream: in a graph the fork / join edges cost no host time (issued eagerly they cost ~3 ms of events
+        per step and make the step host-bound), and the small text / map kernels overlap the 28 224-row ones.  Measured in
+        one call on one MI355X at batch 64: eager 18.83, graph with the weight-gradient stream only 19.32, with the branch
+        stream 18.58 ms/step."""
         branches = ops.Branches.enabled
-        ops.Branches.enabled = branches or self.graph_branches
+        ops.Branches.enabled = True
         try:
             yield
         finally:

@@ -23,8 +23,6 @@ from .arena import ParamArena
 from .config import BevBertConfig
 
 LN_EPS = 1e-12
-# captured steps (a side stream exists): the text-independent front of the map / BEV branches runs beside the text encoder
-EARLY_BEV = __import__("os").environ.get("BEVBERT_EARLY_BEV", "0") == "1"     # measured SLOWER (round 4: 18.39 vs 18.23 ms; round 6: 18.45 vs 17.98 - 18.31): off
 
 
 def gen_seq_masks(seq_lens, max_len):
@@ -358,16 +356,17 @@ class CrossmodalEncoder(_Finalizable):
         self.kv_pw, self.kv_pb = ops._PackedParam(ws, wc, wg), ops._PackedParam(bs, bc, bg)
 
     def hoist_kv(self, context):
-        """Per-layer (B, Lk, 2H) K|V views of ``context`` from one GEMM, or [None] * layers when hoisting is off."""
-        if not ops.HOIST_KV or self.kv_pw is None or self.num_x_layers < 2:
+        """Per-layer (B, Lk, 2H) K|V views of ``context`` from one GEMM, or [None] * layers without packed K|V weights (no arena
+        yet) or with a single layer."""
+        if self.kv_pw is None or self.num_x_layers < 2:
             return [None] * self.num_x_layers
         return ops.hoisted_kv(context, self.kv_pw, self.kv_pb, self.num_x_layers)
 
     def packed_kv(self, context):
-        """Inference only: the (B, Lk, layers * 2H) tensor ``hoist_kv`` slices, or None when hoisting is off.  A rollout
+        """Inference only: the (B, Lk, layers * 2H) tensor ``hoist_kv`` slices, or None where it does not hoist.  A rollout
         computes it once per episode for the instruction (the text states are never updated in the map encoders,
         vilmodel.py:383-398) and hands it back through ``forward(..., kvs=split_kv(packed))`` at every navigation step."""
-        if not ops.HOIST_KV or self.kv_pw is None or self.num_x_layers < 2:
+        if self.kv_pw is None or self.num_x_layers < 2:
             return None
         with torch.no_grad():
             return ops._linear_fwd(context, self.kv_pw.compute, self.kv_pb.compute)
@@ -397,12 +396,9 @@ class CrossmodalEncoder(_Finalizable):
             img_embeds = layer(txt_embeds, tm, self._watch(k, img_embeds), im, graph_sprels=sp, ctx_kv=kv)
         return img_embeds
 
-    def forward_lang2visn(self, txt_embeds, txt_key_mask, visn_feats, visn_key_mask, kvs=None):
-        """The MLM direction (vilmodel.py:790-800): text queries over fixed map / BEV tokens in every layer.  ``kvs``: the
-        hoisted K|V projections of ``visn_feats`` if the caller computed them ahead (they do not depend on the text)."""
-        if kvs is None:
-            kvs = self.hoist_kv(visn_feats)
-        for k, (layer, kv) in enumerate(zip(self.x_layers, kvs)):
+    def forward_lang2visn(self, txt_embeds, txt_key_mask, visn_feats, visn_key_mask):
+        """The MLM direction (vilmodel.py:790-800): text queries over fixed map / BEV tokens in every layer."""
+        for k, (layer, kv) in enumerate(zip(self.x_layers, self.hoist_kv(visn_feats))):
             txt_embeds = layer.forward_lang2visn(self._watch(k, txt_embeds), txt_key_mask, visn_feats, visn_key_mask, ctx_kv=kv)
         return txt_embeds
 
@@ -661,10 +657,9 @@ class LocalBEVEncoder(nn.Module):
         return torch.cat([bev_embeds, obj_embeds], 1), torch.cat([bev_masks, obj_masks], 1)
 
     def forward(self, txt_embeds, txt_masks, bev_fts, bev_pos_fts, bev_masks, bev_nav_masks, obj_embeds, obj_masks,
-                bev_in=None, txt_kvs=None):
-        """``bev_in``: the input embedding if the caller has computed it already (on a side stream, beside the text
-        encoder: it does not depend on the text).  ``txt_kvs``: CrossmodalEncoder.split_kv of a cached packed_kv."""
-        bev_embeds = bev_in if bev_in is not None else self.bev_input_embedding(bev_fts, bev_pos_fts, bev_nav_masks)
+                txt_kvs=None):
+        """``txt_kvs``: CrossmodalEncoder.split_kv of a cached packed_kv."""
+        bev_embeds = self.bev_input_embedding(bev_fts, bev_pos_fts, bev_nav_masks)
         x, m = self.with_objects(bev_embeds, bev_masks, obj_embeds, obj_masks)
         x = self.encoder(txt_embeds, txt_masks, x.contiguous(), m, kvs=txt_kvs)
         K = self.bev_dim * self.bev_dim
@@ -854,17 +849,9 @@ class GlocalTextPathCMT(nn.Module):
                                   traj_vp_obj_lens, traj_view_dep_fts)
             tok_lens, ol_host = self._token_lens_host(traj_vp_view_lens, traj_vp_obj_lens, view_lens_host,
                                                       obj_lens_host)
-        # ... and, behind it, the BEV input embedding (28 224-row GEMM + two LayerNorms): it does not depend on the text
-        # either, and the text encoder's 5 120-row kernels leave most of the chip idle (round-4 timeline: 1.3 busy queues
-        # on average during the first 4.3 ms of a step)
-        bev_in = None
-        if br.on and EARLY_BEV and not has_obj:
-            br.fork(bev_fts, bev_pos_fts, bev_nav_masks)
-            with br.side():
-                bev_in = self.local_encoder.bev_input_embedding(bev_fts, bev_pos_fts, bev_nav_masks)
+        # The BEV input embedding does not depend on the text either, but stays behind the text encoder on the current
+        # stream: issued beside it on the side stream, the step measured slower (18.39 vs 18.23 ms; 18.45 vs 17.98 - 18.31)
         txt_embeds, txt_masks = self._text(txt_ids, txt_lens)
-        if bev_in is not None:
-            br.join(bev_in)
         if has_obj:             # the object tokens feed the BEV branch: they are needed on the current stream
             br.join(traj)
             obj_embeds, obj_masks = self._obj_tokens(traj, traj_step_lens, traj_vp_view_lens, traj_vp_obj_lens,
@@ -878,8 +865,7 @@ class GlocalTextPathCMT(nn.Module):
                                                   tok_lens, gmap_csr)
                 gmap_embeds = self.global_encoder(txt_embeds, txt_masks, g_in, g_masks, gmap_pair_dists)
         bev_embeds, obj_embeds = self.local_encoder(txt_embeds, txt_masks, bev_fts, bev_pos_fts,
-                                                    _all_ones_to_none(bev_masks), bev_nav_masks, obj_embeds, obj_masks,
-                                                    bev_in=bev_in)
+                                                    _all_ones_to_none(bev_masks), bev_nav_masks, obj_embeds, obj_masks)
         br.join(gmap_embeds)
         return gmap_embeds, bev_embeds, obj_embeds, obj_masks
 
@@ -892,34 +878,19 @@ class GlocalTextPathCMT(nn.Module):
         br.fork(traj_view_img_fts, traj_loc_fts, traj_nav_types, traj_vp_view_lens, traj_obj_img_fts, traj_vp_obj_lens,
                 traj_view_dep_fts, bev_fts, bev_pos_fts, bev_nav_masks, gmap_step_ids, gmap_pos_fts, gmap_lens)
         tok_lens, ol_host = self._token_lens_host(traj_vp_view_lens, traj_vp_obj_lens, view_lens_host, obj_lens_host)
-        early = br.on and EARLY_BEV and traj_obj_img_fts is None
-        g_in = g_masks = g_kvs = bev_in = bev_kvs = None
         with br.side():         # panorama encoder next to the text encoder
             traj = self._traj(traj_view_img_fts, traj_loc_fts, traj_nav_types, traj_vp_view_lens, traj_obj_img_fts,
                               traj_vp_obj_lens, traj_view_dep_fts)
-            if early:
-                # ... and everything else of the step that does not depend on the text: the map / BEV input embeddings and
-                # the K|V projections of all cross-attention layers over them (one 28 224 x 6 144 x 768 GEMM for the BEV):
-                # ~0.5 ms of large kernels beside the text encoder's small ones instead of behind them
-                g_in, g_masks = self._gmap_inputs(traj, traj_step_lens, traj_vp_view_lens, traj_vpids, traj_cand_vpids,
-                                                  gmap_vpids, gmap_step_ids, gmap_pos_fts, gmap_lens, tok_lens, gmap_csr)
-                g_kvs = self.global_encoder.encoder.hoist_kv(g_in)
-                bev_in = self.local_encoder.bev_input_embedding(bev_fts, bev_pos_fts, bev_nav_masks).contiguous()
-                bev_kvs = self.local_encoder.encoder.hoist_kv(bev_in)
         txt_embeds, txt_masks = self._text(txt_ids, txt_lens)
         tm = neg_key_mask(txt_masks)
-        if early:
-            br.join(bev_in, *[t for t in bev_kvs if t is not None])
         # side stream: text queries over the global map;  current stream: text queries over the BEV (+ objects)
         br.fork(txt_embeds, tm, gmap_step_ids, gmap_pos_fts, gmap_lens)
         with br.side():
-            if not early:
-                g_in, g_masks = self._gmap_inputs(traj, traj_step_lens, traj_vp_view_lens, traj_vpids, traj_cand_vpids,
-                                                  gmap_vpids, gmap_step_ids, gmap_pos_fts, gmap_lens, tok_lens, gmap_csr)
+            g_in, g_masks = self._gmap_inputs(traj, traj_step_lens, traj_vp_view_lens, traj_vpids, traj_cand_vpids,
+                                              gmap_vpids, gmap_step_ids, gmap_pos_fts, gmap_lens, tok_lens, gmap_csr)
             gm = neg_key_mask(g_masks)
-            g_txt = self.global_encoder.encoder.forward_lang2visn(txt_embeds, tm, g_in, gm, kvs=g_kvs)
-        if not early:
-            bev_in = self.local_encoder.bev_input_embedding(bev_fts, bev_pos_fts, bev_nav_masks)
+            g_txt = self.global_encoder.encoder.forward_lang2visn(txt_embeds, tm, g_in, gm)
+        bev_in = self.local_encoder.bev_input_embedding(bev_fts, bev_pos_fts, bev_nav_masks)
         obj_embeds = obj_masks = None
         if traj_obj_img_fts is not None:
             br.join(traj)
@@ -929,7 +900,7 @@ class GlocalTextPathCMT(nn.Module):
                                                                 obj_masks)
         bev_in = bev_in.contiguous()
         bm = neg_key_mask(bev_obj_masks)
-        b_txt = self.local_encoder.encoder.forward_lang2visn(txt_embeds, tm, bev_in, bm, kvs=bev_kvs)
+        b_txt = self.local_encoder.encoder.forward_lang2visn(txt_embeds, tm, bev_in, bm)
         br.join(g_txt)
         return g_txt + b_txt
 
