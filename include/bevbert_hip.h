@@ -900,6 +900,21 @@ int bevbert_dr_gn_relu_maxpool(const float* x, const float* mean, const float* r
 int bevbert_dr_gather_rows(const void* x, void* out, int N, int H, int W, int C, int ksize, int stride, int dtype,
                            hipStream_t stream);
 
+/* ---- R2R pre-training inputs from device-resident tables (csrc/path_data.hip, path_data.py, feature_store.py) ----------
+ * The panorama tensors of a batch, gathered from a resident view-feature store and the per-viewpoint PanoTable instead of
+ * being collated on the host (pretrain_src/data/dataset.py:580-622 get_traj_pano_fts, tasks.py:126-137 the collates'
+ * pad_tensors, loader.py:78-120 the copy).  store (N, n_views, view_stride) f16: only the first D channels of a view are
+ * read (the reference slices [:, :image_feat_size] off rows that may carry class probabilities).  PanoTable: view_order
+ * (N, Vmax) u8 the store view of token v, n_tokens (N), loc_tab (N, Vmax, L) f32, nav_tab (N, Vmax) u8.  rows (Tp): the
+ * batch's panoramas as store / table rows, -1 = a dummy panorama.  Written: img (Tp, Vp, D) f32 (the widening is exact), loc
+ * (Tp, Vp, L) f32, nav (Tp, Vp) i64, lens (Tp) i64; everything beyond a panorama's token count is zero; a dummy panorama is
+ * all zeros with length 1.  16-byte loads where D, view_stride and the pointers allow, single elements otherwise.  No
+ * atomics.  The CALLER checks 0 <= rows < N or -1 and n_tokens <= Vp (device data is not read back here); a row >= N is
+ * written as a dummy and tokens beyond Vp are dropped rather than written out of bounds. */
+int bevbert_pd_pano_rows(const void* store, int64_t view_stride, int n_views, const uint8_t* view_order, const int* n_tokens,
+                         const float* loc_tab, const uint8_t* nav_tab, const int* rows, float* img, float* loc, int64_t* nav,
+                         int64_t* lens, int N, int Vmax, int L, int Tp, int Vp, int D, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

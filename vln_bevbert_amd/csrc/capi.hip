@@ -37,7 +37,7 @@ BEVBERT_API int bevbert_zero(void* p, int64_t bytes, hipStream_t stream) {
   return BB_OK;
 }
 
-BEVBERT_API int bevbert_version(void) { return 500; }  // 0.5.0: float16 attention forward (csrc/attn_fwd2.hip), fp16 ViT row kernels and GEMMs
+BEVBERT_API int bevbert_version(void) { return 600; }  // 0.6.0: bevbert_pd_pano_rows (csrc/path_data.hip), entry point added
 
 static const uint32_t* g_step_salt = nullptr;
 const uint32_t* bb_step_salt() { return g_step_salt; }

@@ -22,7 +22,7 @@ CSRC = os.path.join(_HERE, "csrc")
 # instructions of the SIMD's other wave while plain ones do (scripts/probes/mfma_valu_overlap.hip,
 # profiles/r05_mfma_valu_overlap_probe.txt).  Measured on that kernel: no difference either way.
 EXTRA_FLAGS = {"attn_fwd4.hip": ["-fno-slp-vectorize"]}
-SOURCES = ["splat.hip", "layernorm.hip", "colwise.hip", "optimizer.hip", "gather.hip", "pointwise.hip", "attn_simple.hip", "attn_f32.hip", "attn_mfma.hip", "attn_bwd1.hip", "attn_fwd2.hip", "attn_fwd4.hip", "attn_bwd7p1.hip", "attn_small.hip", "attn_short.hip", "smallk.hip", "sap_loss.hip", "graph_nav.hip", "nav_expert.hip", "nav_obj.hip", "waypoint.hip", "ce_map.hip", "ce_train.hip", "val_metrics.hip", "vit.hip", "depth_resnet.hip", "gemm.hip", "capi.hip"]
+SOURCES = ["splat.hip", "layernorm.hip", "colwise.hip", "optimizer.hip", "gather.hip", "pointwise.hip", "attn_simple.hip", "attn_f32.hip", "attn_mfma.hip", "attn_bwd1.hip", "attn_fwd2.hip", "attn_fwd4.hip", "attn_bwd7p1.hip", "attn_small.hip", "attn_short.hip", "smallk.hip", "sap_loss.hip", "graph_nav.hip", "nav_expert.hip", "nav_obj.hip", "waypoint.hip", "ce_map.hip", "ce_train.hip", "val_metrics.hip", "vit.hip", "depth_resnet.hip", "path_data.hip", "gemm.hip", "capi.hip"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "bevbert_hip.h")
 
 F32, BF16, F16 = 0, 1, 2

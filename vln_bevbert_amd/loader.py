@@ -6,7 +6,7 @@ step in ``MetaLoader`` (loader.py:18-62).  Everything it then does on the HOST i
 masked tokens, the SAP fusion table, the global-map aggregation lists (vilmodel.py:632-666, pretrain_cmt.py:339-356) --
 is loader work here (``StaticBatch._host_side``), done by the producer thread of ``StreamingLoader`` next to the copies:
 
-    source iterator (task, host batch)            main thread
+    source iterator (task, host batch[, grid keys[, pano rows]])      main thread
           |  producer thread                           |
           v                                            v
     BucketManager.acquire: shape signature -> buffer set of that bucket (round robin over ``depth`` sets; waits for the
@@ -42,13 +42,17 @@ class BucketManager:
 
     WAIT_TIMEOUT_S = 120.0       # a consumer that never releases is a bug: say so instead of hanging forever
 
-    def __init__(self, cfg, device, depth=2, max_buckets=16, grid_store=None, obj_static=False):
+    def __init__(self, cfg, device, depth=2, max_buckets=16, grid_store=None, obj_static=False, view_store=None,
+                 pano_table=None):
         device = torch.device(device)
         if device.type == "cuda" and device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
         self.cfg, self.device, self.depth, self.max_buckets = cfg, device, depth, max_buckets
         self.grid_store = grid_store
         self.obj_static = obj_static        # passed through to StaticBatch: object-token batches padded and capturable
+        # by-reference panoramas (feature_store.ViewFeatureStore + path_data.PanoTable): batches come with ``pano_rows`` and
+        # the panorama tensors are gathered on the copy stream by StaticBatch, behind the copies of the same refill
+        self.view_store, self.pano_table = view_store, pano_table
         self.buckets = collections.OrderedDict()        # signature -> {"sets": [StaticBatch], "next": int}
         self.copy_stream_probe = None
         self.copy_stream = pick_copy_stream(self.device, self) if self.device.type == "cuda" else None
@@ -79,11 +83,14 @@ class BucketManager:
             done.synchronize()                          # host order: the host-side fields are rewritten below too
         self.stats["wait_s"] += time.perf_counter() - t0      # time spent waiting (consumer + GPU), not loader work
 
-    def acquire(self, task, batch, grid_keys=None, stop=None):
+    def acquire(self, task, batch, grid_keys=None, stop=None, pano_rows=None):
         """Device-resident StaticBatch holding ``batch`` (host tensors, collate schema).  Blocks while the buffer set it
         is about to overwrite is still held by the consumer or read by an earlier step; ``stop`` (a threading.Event owned
-        by the calling loader) ends such a wait with LoaderStopped."""
+        by the calling loader) ends such a wait with LoaderStopped.  ``pano_rows``: the batch's panoramas as rows of the
+        manager's view store (path_data.PathBatchSource), in place of the panorama tensors."""
         t0 = time.perf_counter()
+        if pano_rows is not None:
+            batch = dict(batch, pano_rows=pano_rows)
         host = StaticBatch.plan(self.cfg, task, batch, obj_static=self.obj_static)
         sig = host["signature"]
         b = self.buckets.get(sig)
@@ -102,7 +109,7 @@ class BucketManager:
         if len(b["sets"]) < self.depth:                  # first uses of a bucket: allocate another buffer set
             with self._on_copy_stream():
                 sb = StaticBatch(self.cfg, task, batch, self.device, grid_store=self.grid_store, grid_keys=grid_keys,
-                                 obj_static=self.obj_static)
+                                 obj_static=self.obj_static, view_store=self.view_store, pano_table=self.pano_table)
                 sb.ready = self._record()
             sb.done = None
             b["sets"].append(sb)
@@ -209,7 +216,8 @@ class StreamingLoader:
                 st["source_s"] += time.perf_counter() - t0          # waiting for the collate workers / the dataset
                 task, batch = item[0], item[1]
                 keys = item[2] if len(item) > 2 else None
-                sb = self.manager.acquire(task, batch, grid_keys=keys, stop=self._stop_token)
+                sb = self.manager.acquire(task, batch, grid_keys=keys, stop=self._stop_token,
+                                          pano_rows=item[3] if len(item) > 3 else None)
                 t0 = time.perf_counter()
                 self.q.put((task, sb))
                 st["queue_s"] += time.perf_counter() - t0           # waiting for the consumer to take the previous batch

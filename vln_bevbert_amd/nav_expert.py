@@ -184,6 +184,27 @@ class ScanGraphs:
     def node(self, scan, vp):
         return self.index[(scan, vp)]
 
+    @property
+    def hops(self):
+        """(S, N, N) int16: edges on the shortest path u -> v (``len(shortest_paths[u][v]) - 1``), -1 where there is none.
+        Built on first use from the pred table: a node is one hop further than its predecessor."""
+        if getattr(self, "_hops", None) is None:
+            S, N = len(self.scans), self.n_max
+            h = np.full((S, N, N), -1, dtype=np.int16)
+            for si, ids in enumerate(self.ids):
+                k = np.arange(len(ids))
+                h[si, k, k] = 0
+            has = self.pred >= 0
+            parent = np.where(has, self.pred, 0).astype(np.int64)
+            while True:
+                ph = np.take_along_axis(h, parent, axis=2)
+                new = np.where(has & (ph >= 0), ph + 1, h).astype(np.int16)
+                if np.array_equal(new, h):
+                    break
+                h = new
+            self._hops = h
+        return self._hops
+
     def to(self, device):
         """(dist, pred) on `device`, uploaded once per device."""
         key = str(device)

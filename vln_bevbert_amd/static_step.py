@@ -61,13 +61,21 @@ def _round_up(n, m):
 class StaticBatch:
     """Device buffers + loader-built index tensors of one batch of one task, in a fixed shape bucket."""
 
-    def __init__(self, cfg, task, batch, device, grid_store=None, grid_keys=None, obj_static=False):
+    def __init__(self, cfg, task, batch, device, grid_store=None, grid_keys=None, obj_static=False, view_store=None,
+                 pano_table=None):
         """``batch``: the collate output on the host (synthetic.collate / the reference's *_collate schema).
         ``grid_store`` + ``grid_keys``: draw the grid features from a device-resident GridFeatureStore instead of
         shipping ``rgbs`` / ``depths`` / ``sems`` (the keys name the samples' viewpoints).
-        ``obj_static``: pad an object-token batch like any other and ship its object / MRC row tables (see OBJ_PAD)."""
+        ``obj_static``: pad an object-token batch like any other and ship its object / MRC row tables (see OBJ_PAD).
+        ``view_store`` + ``pano_table`` (feature_store.ViewFeatureStore, path_data.PanoTable): the batch names its
+        panoramas by ``pano_rows`` (T,) int32 instead of carrying traj_view_img_fts / traj_loc_fts / traj_nav_types
+        (path_data.collate's by-reference form); the four panorama buffers are allocated here and filled on the device
+        by one gather launch (csrc/path_data.hip), here and at every ``load``."""
         self.cfg, self.task, self.device = cfg, task, torch.device(device)
         self.obj_static = bool(obj_static)
+        if (view_store is None) != (pano_table is None) or (view_store is None) != ("pano_rows" not in batch):
+            raise ValueError("a by-reference batch needs pano_rows in the batch, view_store= and pano_table= together")
+        self.view_store, self.pano_table = view_store, pano_table
         self.graph = None           # set by PretrainTrainer once the step has been captured on these buffers
         self.loss_out = None
         self.eager_runs = 0
@@ -84,9 +92,19 @@ class StaticBatch:
         for k, v in src.items():
             if grid_store is not None and k in ("rgbs", "depths", "sems"):
                 continue
-            t[k] = v.to(self.device, non_blocking=True) if torch.is_tensor(v) else v
+            if view_store is not None and k == "traj_vp_view_lens":      # the device copy is written by the gather
+                t[k] = torch.empty(v.shape, dtype=v.dtype, device=self.device)
+            else:
+                t[k] = v.to(self.device, non_blocking=True) if torch.is_tensor(v) else v
             if k in synthetic.HOST_COPIES and torch.is_tensor(v):
                 t[k + "_cpu"] = v
+        if view_store is not None:
+            Tp, Vp, D = host["pano_shape"]
+            t["traj_view_img_fts"] = torch.empty((Tp, Vp, D), dtype=torch.float32, device=self.device)
+            t["traj_loc_fts"] = torch.empty((Tp, Vp, pano_table.loc_fts.shape[2]), dtype=torch.float32, device=self.device)
+            t["traj_nav_types"] = torch.empty((Tp, Vp), dtype=torch.int64, device=self.device)
+            self.tensors = t
+            self._gather_panos(src["pano_rows"])
         t["gmap_csr"] = (ops.SegmentCSR(*host["csr"], self.device, capacity=host["csr_capacity"]), host["G"])
         st = {k: (v.to(self.device, non_blocking=True) if torch.is_tensor(v) else v) for k, v in host["static"].items()}
         t["_static"] = st
@@ -135,7 +153,11 @@ class StaticBatch:
         # ---- panorama count and view count (object-token batches without ``obj_static`` run eagerly anyway: left as they are)
         view_lens = batch["traj_vp_view_lens"]
         obj_lens = batch.get("traj_vp_obj_lens")
-        T0, V0 = batch["traj_view_img_fts"].shape[:2]
+        img = batch.get("traj_view_img_fts")
+        if img is None:     # by reference (pano_rows): the shape pad_tensors would have given the panorama tensors
+            T0, V0, feat = int(view_lens.numel()), int(view_lens.max()), (int(cfg.image_feat_size),)
+        else:
+            T0, V0, feat = int(img.shape[0]), int(img.shape[1]), tuple(img.shape[2:])
         Tp, Vp = (T0, V0) if has_obj and not obj_static else (_round_up(T0, PANO_PAD), _round_up(V0, VIEW_PAD))
         n_views = batch["traj_loc_fts"].shape[1] if has_obj else Vp        # objects: the joint [views | objects] token axis
         widths = {} if has_obj else {k: Vp for k in ("traj_view_img_fts", "traj_loc_fts", "traj_nav_types", "traj_view_dep_fts")}
@@ -155,6 +177,8 @@ class StaticBatch:
         if Tp != T0:
             view_lens = torch.cat([view_lens, view_lens.new_ones(Tp - T0)])
             padded["traj_vp_view_lens"] = view_lens
+            if batch.get("pano_rows") is not None:             # dummy panoramas: row -1
+                padded["pano_rows"] = torch.cat([batch["pano_rows"], batch["pano_rows"].new_full((Tp - T0,), -1)])
             if obj_lens is not None:
                 obj_lens = torch.cat([obj_lens, obj_lens.new_zeros(Tp - T0)])
                 padded["traj_vp_obj_lens"] = obj_lens
@@ -179,7 +203,7 @@ class StaticBatch:
         seq_masks(batch["gmap_lens"], G, "gmap")
         if not has_obj:
             seq_masks(view_lens, Vp, "pano", inf=True)
-        sig = [task, B, txt_shape, (Tp, Vp) + tuple(batch["traj_view_img_fts"].shape[2:]), G]
+        sig = [task, B, txt_shape, (Tp, Vp) + feat, G]
         if obj_static:
             # the panorama encoder's masks over the joint axis (hung on traj_vp_view_lens; ImageEmbeddings.embed looks there)
             seq_masks(lens, n_views, "pano", inf=True)
@@ -244,13 +268,15 @@ class StaticBatch:
         elif task.startswith("sem"):
             static["sem_cap"] = B * cfg.bev_dim * cfg.bev_dim
         return {"padded": padded, "static": static, "csr": (rowptr, idx, w, n_src), "csr_capacity": 2 * n_src, "G": G,
-                "signature": tuple(sig)}
+                "signature": tuple(sig), "pano_shape": (Tp, Vp) + feat}
 
     # -- in-place refill -----------------------------------------------------------------------------------------
     def load(self, batch, grid_keys=None, host=None):
         """Write another batch of the same shape bucket into these buffers (what a prefetching loader does with its
         preallocated device buffers); a captured graph keeps replaying on them.  Raises if the bucket differs.
         ``host``: the result of ``plan`` for this batch if the caller has it already."""
+        if (self.view_store is not None) != ("pano_rows" in batch):
+            raise ValueError("buffers filled by reference take batches with pano_rows, and only those")
         if host is None:
             host = self._host_side(batch)
         if host["signature"] != self.signature:
@@ -260,7 +286,13 @@ class StaticBatch:
         src.update(host["padded"])
         for k, v in src.items():
             if torch.is_tensor(v):
-                if k in t and torch.is_tensor(t[k]):
+                if k == "bev_cand_idxs" and k in t and t[k].shape != v.shape and not self.task.startswith("sap"):
+                    # Only the SAP step reads the candidate cells (pretrain_cmt.py), and only its signature carries their
+                    # count K.  On real paths K is the batch maximum of the last panoramas' candidate counts and moves from
+                    # batch to batch: for the other tasks a refill of another width replaces the tensor, which no captured
+                    # step holds.
+                    t[k] = v.to(self.device, non_blocking=True)
+                elif k in t and torch.is_tensor(t[k]) and not (self.view_store is not None and k == "traj_vp_view_lens"):
                     t[k].copy_(self._staged(k, v), non_blocking=True)
                 if k + "_cpu" in t:
                     t[k + "_cpu"] = v
@@ -275,8 +307,19 @@ class StaticBatch:
                 st[k] = v                      # host integers (row counts): they are part of the shape bucket or a
         if "grid_store" in t and grid_keys is not None:      # divisor the step reads from device memory (see below)
             t["grid_rows"].copy_(t["grid_store"].rows(grid_keys), non_blocking=True)
+        if self.view_store is not None:
+            self._gather_panos(src["pano_rows"])
         self._refresh_counts()
         return self
+
+    def _gather_panos(self, rows_host):
+        """Fill the four panorama buffers from the view store and the PanoTable, on the current stream -- the stream the
+        copies of this refill were issued on (the loader's copy stream), behind the copy of ``pano_rows`` itself, under
+        the same ownership protocol as the copies (loader.BucketManager).  Rows and widths are checked on the host first."""
+        from .feature_store import pano_rows
+        t = self.tensors
+        pano_rows(self.view_store, self.pano_table, rows_host.numpy(), t["pano_rows"], t["traj_view_img_fts"],
+                  t["traj_loc_fts"], t["traj_nav_types"], t["traj_vp_view_lens"])
 
     def _attach_masks(self):
         """Hang the loader-built masks on the device tensors the model derives them from (refills copy in place, so the
